@@ -7,8 +7,14 @@ segments per GPU, RS(k=2, m=1), 8 MiB fragments, device-resident (inputs already
 the timed region starts). A "step" is one batched encode launch over the rank's 64 segments.
 Bytes counted per segment = (k+m) * F (k fragments read, m written).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config 1|2|3|4|5]
+    python bench.py [--gpus N --steps K --warmup W] [--config 1|2|3|4|5] [--full]
+                    [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...     (one rank per GPU, weak scaling)
+
+A plain run sets up, warms up, times the K steps, writes what the last step computed if
+`--dump-outputs DIR` is given (dump_outputs) and prints the line with the headline figure and the
+timed kernel's `roofline`. Everything else described below (`cpu_baseline`, `extra`, the codec
+kernel timed alone in configs 4 and 5, config 1's GPU comparison) is measured with `--full` only.
 
 `--gpus N` alone (no WORLD_SIZE in the environment) starts the N ranks itself: the process counts
 the visible GPUs without initialising HIP and runs torch.distributed.run as a child. Fewer GPUs
@@ -172,6 +178,41 @@ def cpu_sha256(k: int, m: int, F: int, target_s: float) -> dict:
             "value_1thread": round(min(nfrag, 64) * F / t1 / GB, 3)}
 
 
+DUMP_WHOLE = 1 << 21   # elements up to which --dump-outputs writes an array whole
+DUMP_BLOCKS = 1 << 20  # block sums written of a larger one
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs DIR: what the timed path computed in its last step (the arrays its caller
+    receives; numpy arrays or torch tensors), so that two builds can be compared output for
+    output. The same arguments give the same inputs: the counter generator and the erasure
+    patterns are seeded. An array of up to DUMP_WHOLE elements goes whole to DIR/<name>.npy
+    (float32). A larger one goes as DIR/<name>_sample.npy (float32: its elements at up to
+    DUMP_WHOLE fixed, seeded positions, in ascending order of position) and DIR/<name>_blocksum.npy
+    (float64: the sums of its consecutive equal blocks, at most DUMP_BLOCKS + 1 of them, the last
+    one the remainder; exact for bytes, and every element counts). At most 16 MiB per array."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        t = torch.from_numpy(np.ascontiguousarray(arr)) if isinstance(arr, np.ndarray) else arr
+        flat = t.contiguous().view(-1)
+        n = flat.numel()
+        if n <= DUMP_WHOLE:
+            np.save(os.path.join(path, f"{name}.npy"), flat.cpu().numpy().astype(np.float32))
+            continue
+        idx = np.unique(np.random.default_rng(0xD0).integers(0, n, DUMP_WHOLE))
+        got = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(path, f"{name}_sample.npy"), got.cpu().numpy().astype(np.float32))
+        block = -(-n // DUMP_BLOCKS)
+        nb = n // block
+        rows = max(1, (1 << 28) // block)  # 256 Mi elements per reduction
+        sums = [flat[r * block:min(r + rows, nb) * block].view(-1, block).sum(1, dtype=torch.float64)
+                for r in range(0, nb, rows)]
+        if nb * block < n:
+            sums.append(flat[nb * block:].sum(dtype=torch.float64).view(1))
+        np.save(os.path.join(path, f"{name}_blocksum.npy"), torch.cat(sums).cpu().numpy())
+
+
 def config1_cpu(args) -> dict:
     """BASELINE config 1: one 16 MiB segment, RS(2,1): encode + the 3 single-erasure rebuilds,
     on the CPU codec (oracle/rs_oracle.c, kind "port": the reference has no codec), at 1 thread
@@ -213,6 +254,10 @@ def config1_cpu(args) -> dict:
         "note": "the reference ships no codec (SURVEY.md §0.1); the CPU codec is this repo's C "
                 "restatement of klauspost/reedsolomon",
     }
+    if args.dump_outputs:  # the segment's shards as the last rebuild left them
+        dump_outputs(args.dump_outputs, {f"shard{i}": s for i, s in enumerate(shards)})
+    if not args.full:
+        return res
     try:
         import torch
         if torch.cuda.is_available():
@@ -1137,7 +1182,8 @@ def guarded(leg, *a) -> dict:
 
 
 def line_problems(out: dict) -> list:
-    """What a bench line lacks against the driver's contract and VERDICT's asks (empty = none):
+    """What a `--full` bench line lacks against the driver's contract and VERDICT's asks (empty =
+    none; a plain run's line carries neither `cpu_baseline` nor `extra`):
     the contract keys, `roofline` and `cpu_baseline` at every N (at N > 1 on the CPU share of the
     GPUs held), and for the default config: config 4's 64 GiB strong-scaling encode (T_N, T1,
     efficiency, sampled segments bit-exact) at every N; at N = 1 the config-5 step with checked digests and
@@ -1271,13 +1317,25 @@ def main() -> None:
     ap.add_argument("--exchange", choices=["survivors", "partials", "auto"], default="survivors",
                     help="config 4: degraded-read exchange (survivors to the decoder, or partial "
                          "rebuilds from every GPU holding survivors, SURVEY.md §8e)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the CPU "
+                         "baseline, the `extra` legs of the default line, the codec kernel timed "
+                         "alone (configs 4 and 5), config 1's GPU comparison. A plain run sets "
+                         "up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed to "
+                         "DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: leave out the `extra` legs of the default line")
     ap.add_argument("--sweep", type=str, default="",
                     help="comma list of CT variants: interleaved A/B in one process, prints "
                          "median launch ms per variant and exits")
     args = ap.parse_args()
+    if not args.full:  # a plain run measures the headline figure alone
+        args.no_cpu_baseline = args.no_extra = True
     if args.warmup is None:
         args.warmup = 30 if args.config == 6 else 10
 
@@ -1386,6 +1444,8 @@ def main() -> None:
                             args.tick_pf)
         d_hex, tick_blocks = pipe.pipe_hex[0], pipe.tick_blocks
 
+    last = {}  # config 4 with --dump-outputs: the fragments the last step's degraded read rebuilt
+
     def step():
         if args.config in (3, 6, 7):
             enc.ReconstructBatch(d_data, d_par, nseg, F, present, stream=stream)
@@ -1393,7 +1453,9 @@ def main() -> None:
             pipe.step()
         elif args.config == 4:
             enc.EncodeBatch(d_data, d_par, nseg, F, stream=stream)
-            gather[0]()
+            rebuilt = gather[0]()
+            if args.dump_outputs:
+                last["rebuilt"] = rebuilt
         else:
             enc.EncodeBatch(d_data, d_par, nseg, F, stream=stream)
 
@@ -1478,6 +1540,24 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, launch_ms = float(t[0]), float(t[1])
 
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left (rank 0's share): the parity of an encode, the rebuilt
+        # batch of a reconstruct (in place), config 5's parity and digests of the last batch,
+        # config 4's parity and the fragments its degraded read rebuilt
+        if args.config in (3, 6, 7):
+            outs = {"data": d_data, "parity": d_par}
+        elif args.config == 5:
+            b = (pipe.i - 1) % pipe.NB
+            outs = {"parity": pipe.pipe_par[b], "hex": pipe.pipe_hex[b]}
+        else:
+            outs = {"parity": d_par}
+            if last.get("rebuilt"):
+                outs["rebuilt"] = torch.stack([last["rebuilt"][sf]
+                                               for sf in sorted(last["rebuilt"])])
+        dump_outputs(args.dump_outputs, outs)
+        del outs
+        last.clear()
+
     # algorithmic bytes per segment: read k*F, write m*F (encode) or one erased fragment each
     # (config 7 repairs one fragment: (k+1)*F)
     per_seg = (k + (1 if args.config == 7 else
@@ -1496,11 +1576,11 @@ def main() -> None:
         return a.elapsed_time(b) / reps
 
     sha_note = None
-    if args.config == 4:
+    if args.config == 4 and args.full:
         # the step holds encode + the degraded-read gather; the roofline is the encode kernel's
         launch_ms = timed(lambda: enc.EncodeBatch(d_data, d_par, nseg, F, stream=stream), 10)
         achieved = bytes_step_gpu / (launch_ms * 1e-3) / GB
-    if args.config == 5:
+    if args.config == 5 and args.full:
         # the step holds encode + SHA-256; time each kernel alone for the roofline
         enc_ms = timed(lambda: enc.EncodeBatch(d_data, d_par, nseg, F, stream=stream), 20)
         sha_ms = timed(lambda: enc.Sha256Batch(d_data, d_par, nseg, F, d_hex, stream=stream), 3)
@@ -1577,6 +1657,10 @@ def main() -> None:
     }
     if sha_note:
         out["sha256"] = sha_note
+    if args.config in (4, 5) and not args.full:
+        out["roofline"]["basis"] = ("the whole step's time (config 4: with the degraded-read "
+                                    "gather; config 5: with the hash ticks); --full times the "
+                                    "codec kernel alone")
 
     def gather_leg(run_verify_plan, reps=5, code=(k, F)) -> dict:
         """Time the degraded read (exchange over the process group + rebuild) alone,
@@ -1627,7 +1711,7 @@ def main() -> None:
         out["extra"]["host_e2e"] = guarded(host_e2e_leg, dev, local, world, rank, backend)
 
     exchange_pending = cabi_pending = False
-    if args.config == 4:
+    if args.config == 4 and args.full:
         out["degraded_gather"] = gather_leg(gather)
     elif world > 1 and not args.no_extra and args.config == 2:
         # config 4's exchange step measured in the default (scaling) run as well, through both

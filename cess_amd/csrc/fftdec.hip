@@ -271,7 +271,7 @@ __device__ __forceinline__ void dec_m_cols(const Layout& L, uint32_t seg, uint64
 // crossbar (dec_m_cols). The product's: DPP everywhere (kFdmSwz = 0); the IFFT's exchange through
 // the crossbar is no faster one form per process (profiles/r04/swz_standalone_runs.jsonl), the
 // nibble packs through it take the small class past 168 VGPRs.
-constexpr int kFdmSwz = 0;
+[[maybe_unused]] constexpr int kFdmSwz = 0;  // (unused in a CEC_FD_FORM unit)
 template <unsigned SIDE, bool BIG, int SWZ, bool SKIP = true>
 __global__ __launch_bounds__(256) CEC_FD_ATTR void k_fftdec_m(Layout L, const uint32_t* __restrict__ plan1,
                                                   const uint32_t* const* __restrict__ plans,
@@ -289,7 +289,31 @@ __global__ __launch_bounds__(256) CEC_FD_ATTR void k_fftdec_m(Layout L, const ui
                                  (lds_u32*)(lds + (threadIdx.x >> 6) * (LR * 512)));
 }
 
+// the four kernels (side, plan class) of one form
+using fdm_kern_t = void (*)(Layout, const uint32_t*, const uint32_t* const*, const uint32_t*,
+                            uint32_t);
+template <int SWZ, bool SKIP>
+fdm_kern_t fdm_kernel(int side, bool big) {
+  return side ? (big ? k_fftdec_m<1, true, SWZ, SKIP> : k_fftdec_m<1, false, SWZ, SKIP>)
+              : (big ? k_fftdec_m<0, true, SWZ, SKIP> : k_fftdec_m<0, false, SWZ, SKIP>);
+}
+
 }  // namespace
+
+// The tuning build compiles this file once more per form besides the product's
+// (-DCEC_TUNING -DCEC_FD_FORM=<form>), so that the forms' device code builds side by side instead
+// of in one unit (a form's four kernels take minutes to compile). Such a unit defines only
+// fftdec_form_<form>(), which hands launch_fftdec that form's kernels.
+// form = 1 + the SWZ mask; 10 = the product's without the skip of unread slots.
+#define CEC_FD_FORMS(X) X(2) X(4) X(6) X(8) X(10)
+#ifdef CEC_FD_FORM
+#define CEC_FD_DEFINE(f) CEC_FD_DEFINE_(f)
+#define CEC_FD_DEFINE_(f)                                                          \
+  fdm_kern_t fftdec_form_##f(int side, bool big) {                                 \
+    return fdm_kernel<(f == 10 ? 0 : f - 1), f != 10>(side, big);                  \
+  }
+CEC_FD_DEFINE(CEC_FD_FORM)
+#else
 
 bool fftdec_big(int nrs) { return nrs > kSmallNr; }
 
@@ -300,29 +324,21 @@ bool fftdec_layout_ok(const Layout& L) {
          L.shard_stride < (uint64_t(1) << 26);  // 32-bit buffer offsets over a coset
 }
 
+#ifdef CEC_TUNING
+#define CEC_FD_DECLARE(f) fdm_kern_t fftdec_form_##f(int side, bool big);
+CEC_FD_FORMS(CEC_FD_DECLARE)
+#endif
+
 bool launch_fftdec(const Layout& L, int side, bool big, const uint32_t* plan1,
                    const uint32_t* const* plans, const uint32_t* seg_list, uint32_t nseg,
                    hipStream_t st, int form) {
   if (!fftdec_layout_ok(L) || (side != 0 && side != 1)) return false;
   const uint64_t gx = (L.len / 32 * 2 + 255) / 256;
-  auto kern = side ? (big ? k_fftdec_m<1, true, kFdmSwz> : k_fftdec_m<1, false, kFdmSwz>)
-                   : (big ? k_fftdec_m<0, true, kFdmSwz> : k_fftdec_m<0, false, kFdmSwz>);
+  auto kern = fdm_kernel<kFdmSwz, true>(side, big);
 #ifdef CEC_TUNING
-  auto pick = [&](auto S) {
-    constexpr int M = decltype(S)::value;
-    kern = side ? (big ? k_fftdec_m<1, true, M> : k_fftdec_m<1, false, M>)
-                : (big ? k_fftdec_m<0, true, M> : k_fftdec_m<0, false, M>);
-  };
-  switch (form) {  // form = 1 + the SWZ mask
-    case 1: pick(std::integral_constant<int, 0>{}); break;
-    case 2: pick(std::integral_constant<int, 1>{}); break;
-    case 4: pick(std::integral_constant<int, 3>{}); break;
-    case 6: pick(std::integral_constant<int, 5>{}); break;
-    case 8: pick(std::integral_constant<int, 7>{}); break;
-    case 10:  // the product's without the skip of unread slots
-      kern = side ? (big ? k_fftdec_m<1, true, 0, false> : k_fftdec_m<1, false, 0, false>)
-                  : (big ? k_fftdec_m<0, true, 0, false> : k_fftdec_m<0, false, 0, false>);
-      break;
+  switch (form) {  // form 1 (SWZ mask 0) is the product's
+#define CEC_FD_CASE(f) case f: kern = fftdec_form_##f(side, big); break;
+    CEC_FD_FORMS(CEC_FD_CASE)
     default: break;
   }
 #else
@@ -335,5 +351,7 @@ bool launch_fftdec(const Layout& L, int side, bool big, const uint32_t* plan1,
   }
   return true;
 }
+
+#endif  // CEC_FD_FORM
 
 }  // namespace cec

@@ -278,3 +278,65 @@ def test_exchange_legs_torch_error_then_cabi():
     assert ex["degraded_gather_cabi"]["transport"].startswith("libcessec")
     # (the wide legs build an RS(32,32) codec, which needs a GPU: on CPU they record that error)
     assert "NCCL error" not in json.dumps(ex["wide_degraded_gather_cabi"])
+
+
+def test_dump_outputs_files(tmp_path):
+    """bench.dump_outputs (--dump-outputs): a small array goes whole, a large one as a seeded
+    sample plus block sums that count every element; float32 / float64, the same from run to run,
+    numpy arrays and torch tensors alike."""
+    import numpy as np
+    import torch
+    big = (np.arange(bench.DUMP_WHOLE * 2 + 3, dtype=np.uint64) * 2654435761 >> 7).astype(np.uint8)
+    small = np.arange(100, dtype=np.uint8).reshape(4, 25)
+    a, b = tmp_path / "a", tmp_path / "b"
+    bench.dump_outputs(str(a), {"small": small, "big": big})
+    bench.dump_outputs(str(b), {"small": torch.from_numpy(small), "big": torch.from_numpy(big)})
+    assert sorted(os.listdir(a)) == sorted(os.listdir(b)) == [
+        "big_blocksum.npy", "big_sample.npy", "small.npy"]
+    for name in os.listdir(a):
+        assert np.array_equal(np.load(a / name), np.load(b / name))
+    whole = np.load(a / "small.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, small.reshape(-1))
+    sample, sums = np.load(a / "big_sample.npy"), np.load(a / "big_blocksum.npy")
+    assert sample.dtype == np.float32 and 0 < sample.size <= bench.DUMP_WHOLE
+    idx = np.unique(np.random.default_rng(0xD0).integers(0, big.size, bench.DUMP_WHOLE))
+    assert np.array_equal(sample, big[idx])
+    assert sums.dtype == np.float64 and sums.size <= bench.DUMP_BLOCKS + 1
+    block = -(-big.size // bench.DUMP_BLOCKS)
+    assert sums[0] == big[:block].sum() and sums[-1] == big[big.size // block * block:].sum()
+    assert sums.sum() == big.sum(dtype=np.uint64)
+    changed = big.copy()
+    changed[-1] ^= 1  # any element moves a block sum
+    bench.dump_outputs(str(b), {"big": changed})
+    assert not np.array_equal(np.load(b / "big_blocksum.npy"), sums)
+
+
+@pytest.mark.gpu
+def test_plain_run_line_and_dump(tmp_path, corc):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` prints the headline line alone (no
+    cpu_baseline, no extra legs; those are --full's), --steps sets the timed steps, and
+    --dump-outputs writes the last step's parity: equal to the C oracle's encode of the same
+    seeded segments, dumped the same way."""
+    import numpy as np
+    nseg = 2
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--segments", str(nseg),
+              "--dump-outputs", str(tmp_path / "got")], {})
+    assert r.returncode == 0, r.stderr
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["metric"] == bench.METRIC and line["unit"] == "GB/s" and line["dtype"] == "u8"
+    assert line["higher_is_better"] is True and line["value"] > 0
+    assert "cpu_baseline" not in line and "extra" not in line
+    k, m, F = bench.CONFIGS[2][:3]
+    data = np.empty((nseg, k, F), np.uint8)
+    par = np.empty((nseg, m, F), np.uint8)
+    corc.orc_fill_synthetic(data.ctypes.data, k * F, nseg, 0, bench.SEED0 + 2)
+    corc.orc_encode_batch(k, m, data.ctypes.data, par.ctypes.data, nseg, F, 4, 1)
+    bench.dump_outputs(str(tmp_path / "want"), {"parity": par})
+    names = sorted(os.listdir(tmp_path / "want"))
+    assert names == sorted(os.listdir(tmp_path / "got")) == ["parity_blocksum.npy",
+                                                            "parity_sample.npy"]
+    for name in names:
+        assert np.array_equal(np.load(tmp_path / "got" / name), np.load(tmp_path / "want" / name))

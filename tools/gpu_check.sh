@@ -18,7 +18,7 @@ step() {  # step <name> <timeout> cmd...
 }
 step pytest_gpu 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread
 step smoke 180 python -u -c "import __graft_entry__ as g; g.smoke()"
-step bench 400 python -u bench.py "$@"
+step bench 400 python -u bench.py --full "$@"
 cp "$OUT/bench.log" "$OUT/bench.json"
 export TMPDIR=/tmp
 step rocprof 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python -u bench.py --no-cpu-baseline --no-extra "$@"

@@ -16,14 +16,14 @@ run() {  # run <name> <timeout> cmd...
   tail -c 400 "$OUT/$name.out"; echo
   if [ $rc -ne 0 ]; then echo "stopping after $name (rc=$rc)"; tail -5 "$OUT/$name.err"; exit $rc; fi
 }
-run bench_c2 300 python -u bench.py
+run bench_c2 300 python -u bench.py --full
 for c in 2 3 5; do
   run prof_c$c 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c$c" -o run -- \
     python -u bench.py --config $c --no-cpu-baseline --no-extra --steps 100 --warmup 10
 done
-run bench_c3 300 python -u bench.py --config 3 --cpu-seconds 4
-run bench_c5 300 python -u bench.py --config 5 --steps 400 --warmup 20 --cpu-seconds 4
-run bench_c4 300 python -u bench.py --config 4 --steps 5 --warmup 2 --cpu-seconds 4
+run bench_c3 300 python -u bench.py --full --config 3 --cpu-seconds 4
+run bench_c5 300 python -u bench.py --full --config 5 --steps 400 --warmup 20 --cpu-seconds 4
+run bench_c4 300 python -u bench.py --full --config 4 --steps 5 --warmup 2 --cpu-seconds 4
 run pmc_sq_fft 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d "$OUT/pmc_sq_fft" -o run -- \
   python -u bench.py --config 5 --sweep=-1 --steps 2 --warmup 1
 gcc -O2 -pthread tests/native/pipeline_e2e.c -Iinclude -Lcess_amd -lcessec -Loracle/build -loracle \
