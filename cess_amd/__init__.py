@@ -11,6 +11,7 @@ from .reedsolomon import (
     CecError,
     Encoder,
     ErrInvShardNum,
+    ErrInvalidInput,
     ErrMaxShardNum,
     ErrReconstructRequired,
     ErrShardNoData,
@@ -19,6 +20,7 @@ from .reedsolomon import (
     ErrTooFewShards,
     HipError,
     New,
+    decode_rows,
     fill_synthetic,
     sha256_hex_device,
     sha256_hex_host,
@@ -30,4 +32,5 @@ __all__ = [
     "ErrReconstructRequired", "ErrShardNoData", "ErrShardSize", "ErrShortData",
     "ErrTooFewShards", "HipError", "fill_synthetic", "sha256_hex_device", "sha256_hex_host",
     "HashQueue", "sha256_blocks", "records", "ErrTooManySegments", "audit", "xor_batch",
+    "ErrInvalidInput", "decode_rows",
 ]

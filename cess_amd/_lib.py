@@ -63,6 +63,14 @@ SIGNATURES = {
     "cec_encode_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
     "cec_reconstruct_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,
                                       POINTER(c_uint8), c_int, c_int, c_void_p]),
+    "cec_decode_rows": (c_int, [c_int, c_int, POINTER(c_uint8), POINTER(c_uint8),
+                                POINTER(c_uint8), POINTER(c_uint8), POINTER(c_int)]),
+    "cec_reconstruct_some_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,
+                                           POINTER(c_uint8), POINTER(c_uint8), c_int, c_void_p]),
+    "cec_reconstruct_ptrs": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_size_t,
+                                     c_size_t, c_void_p]),
+    "cec_encode_ptrs": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_size_t,
+                                c_size_t, c_void_p]),
     "cec_reconstruct_partial_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,
                                               POINTER(c_uint8), POINTER(c_uint8), c_int,
                                               c_void_p]),

@@ -594,8 +594,9 @@ void scratch_release(cec_codec* c, const Scratch& s, hipStream_t st) {
 }
 
 // Cache keys start with a kind tag, so keys of different kinds never compare equal whatever
-// their lengths: 'F' full rebuild, 'P' partial rebuild (decode LRU); 'S' / 'Q' the per-segment
-// plans of cec_reconstruct_batch / cec_reconstruct_partial_batch.
+// their lengths: 'F' full rebuild, 'P' partial rebuild, 'R' rebuild of a required subset (decode
+// LRU); 'S' / 'Q' / 'T' the per-segment plans of cec_reconstruct_batch /
+// cec_reconstruct_partial_batch / cec_reconstruct_some_batch.
 std::string pattern_key(const uint8_t* present, int n, bool data_only) {
   std::string key(n + 2, '\0');
   key[0] = 'F';
@@ -611,13 +612,43 @@ std::string partial_key(const uint8_t* present, const uint8_t* held, int n, bool
   return key;
 }
 
+// Key of a rebuild of the lost shards flagged in `required` only (ReconstructSome; flags of
+// present shards are ignored): kind 'R', the pattern, then the wanted flags. A subset that names
+// every shard the full rebuild writes is the full rebuild and gets its 'F' key, so entries and keys
+// of the calls without `required` are exactly what they were. `want` (n flags) receives the
+// normalised subset.
+std::string some_key(const uint8_t* present, const uint8_t* required, int k, int n,
+                     bool data_only, uint8_t* want) {
+  std::string key = pattern_key(present, n, data_only);
+  bool all = true;
+  for (int i = 0; i < n; ++i) {
+    const bool lost = !present[i] && !(data_only && i >= k);
+    want[i] = lost && (!required || required[i]) ? 1 : 0;
+    if (lost && !want[i]) all = false;
+  }
+  if (all) return key;
+  key[0] = 'R';
+  for (int i = 0; i < n; ++i) key.push_back((char)want[i]);
+  return key;
+}
+
 // Decode program for one erasure pattern (LRU-cached). Nothing is evicted here: the caller
 // evicts after its launches are enqueued and marked (evict_decode), so a program resolved
-// earlier in the same call is never dropped under it.
+// earlier in the same call is never dropped under it. With `required`, only the lost shards it
+// flags are outputs (rows of the same decode: the survivors read do not change).
 int get_decode(cec_codec* c, const uint8_t* present, bool data_only, ProgPtr* out,
-               HostImages* keep = nullptr) {
+               HostImages* keep = nullptr, const uint8_t* required = nullptr) {
   const int n = c->k + c->m;
-  std::string key = pattern_key(present, n, data_only);
+  uint8_t want[cec::kMaxShards];
+  std::string key = required ? some_key(present, required, c->k, n, data_only, want)
+                             : pattern_key(present, n, data_only);
+  const bool some = key[0] == 'R';
+  if (some && !std::memchr(want, 1, n)) {
+    // nothing asked for: nothing to do, whatever is present (klauspost returns before it counts
+    // the shards)
+    *out = std::make_shared<const Program>();
+    return CEC_OK;
+  }
   auto it = c->decode_cache.find(key);
   if (it != c->decode_cache.end()) {
     c->lru.splice(c->lru.begin(), c->lru, it->second.lru);
@@ -632,6 +663,19 @@ int get_decode(cec_codec* c, const uint8_t* present, bool data_only, ProgPtr* ou
       cec::gf_decode_plan_sys(c->k, c->m, flags, data_only, *c->E, *plan, sc.a, sc.ainv, sc.work,
                               rd) != 0)
     return set_err(CEC_ETOOFEW, "fewer than k shards present");
+  if (some) {  // keep the wanted rows
+    int w = 0;
+    for (int o = 0; o < plan->nout; ++o) {
+      if (!want[plan->out_idx[o]]) continue;
+      if (w != o) {
+        plan->out_idx[w] = plan->out_idx[o];
+        std::memcpy(plan->coef.v[w], plan->coef.v[o], c->k);
+      }
+      ++w;
+    }
+    plan->nout = w;
+    plan->coef.rows = w;
+  }
   ProgPtr prog;
   if (plan->nout > 0) {
     // RS(32,32) rebuilds of several shards: also the FFT-domain plan (picked at launch by the
@@ -643,8 +687,9 @@ int get_decode(cec_codec* c, const uint8_t* present, bool data_only, ProgPtr* ou
     const bool wide = c->k == 32 && c->m == 32 && plan->nout >= 2;
     uint8_t read[cec::kMaxShards] = {};
     for (int j = 0; j < c->k; ++j) read[plan->in_idx[j]] = 1;
-    const bool fd = wide && cec::fftdec_plan_m(read, flags, data_only, &fdp);
-    const bool fdd = wide && cec::fftdec_plan_d(read, flags, data_only, &fddp);
+    const uint8_t* wf = some ? want : nullptr;  // the plans' output lists shrink to the subset
+    const bool fd = wide && cec::fftdec_plan_m(read, flags, data_only, &fdp, wf);
+    const bool fdd = wide && cec::fftdec_plan_d(read, flags, data_only, &fddp, wf);
     int rc = build_program(c->pool, c->stream, plan->in_idx, c->k, plan->out_idx, plan->nout,
                            plan->coef, &prog, false, keep, fd ? &fdp : nullptr,
                            fdd ? &fddp : nullptr);
@@ -831,12 +876,13 @@ Layout stage_layout(cec_codec* c, size_t len) {
 // Build the plan of a per-segment reconstruct for the pattern array `pkey` (nseg * n flags +
 // data_only + force_generic) into *out; device arrays are uploaded and complete on return.
 // partial: pkey holds 2n flags per segment (present, then held) and the programs are partial
-// (cec_reconstruct_partial_batch).
+// (cec_reconstruct_partial_batch). some: pkey holds 2n flags per segment (present, then required)
+// and the programs write the required lost shards only (cec_reconstruct_some_batch).
 int build_ps_plan(cec_codec* c, const std::string& pkey, size_t nseg, bool data_only,
                   std::unique_ptr<PsPlan>* out, bool partial = false, bool fdok = false,
-                  size_t shard_len = 0) {
+                  size_t shard_len = 0, bool some = false) {
   const int n = c->k + c->m;
-  const int per = partial ? 2 * n : n;
+  const int per = partial || some ? 2 * n : n;
   auto plan = std::make_unique<PsPlan>();
   plan->key = pkey;
   // group segments by pattern, in first-appearance order (deterministic launch order)
@@ -868,9 +914,11 @@ int build_ps_plan(cec_codec* c, const std::string& pkey, size_t nseg, bool data_
     ProgPtr p;
     const uint8_t* flags = reinterpret_cast<const uint8_t*>(g.first.data());
     int rc = partial ? get_partial(c, flags, flags + n, data_only, &p, &up.arena)
-                     : get_decode(c, flags, data_only, &p, &up.arena);
+                     : get_decode(c, flags, data_only, &p, &up.arena, some ? flags + n : nullptr);
     if (rc) return rc;
+    uint8_t want[cec::kMaxShards];
     plan->keys.push_back(partial ? partial_key(flags, flags + n, n, data_only)
+                         : some  ? some_key(flags, flags + n, c->k, n, data_only, want)
                                  : pattern_key(flags, n, data_only));
     if (!p->nout) continue;
     plan->progs.push_back(p);
@@ -1205,9 +1253,12 @@ int cec_encode_batch(cec_codec* c, const uint8_t* d_data, uint8_t* d_parity, siz
   return do_encode(c, L, nullptr, (uint32_t)nseg, pick_stream(c, hip_stream));
 }
 
-int cec_reconstruct_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size_t nseg,
-                          size_t shard_len, const uint8_t* present, int per_segment,
-                          int data_only, void* hip_stream) {
+// cec_reconstruct_batch (required == NULL) and cec_reconstruct_some_batch (required: the same
+// shape as present).
+static int reconstruct_batch_impl(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size_t nseg,
+                                  size_t shard_len, const uint8_t* present,
+                                  const uint8_t* required, int per_segment, int data_only,
+                                  void* hip_stream) {
   if (!c || !present || (nseg && (!d_data || !d_parity))) return set_err(CEC_EINVAL, "null");
   if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
   if (nseg > 0xffffffffull) return set_err(CEC_EINVAL, "too many segments");
@@ -1218,7 +1269,7 @@ int cec_reconstruct_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size
   int rc = CEC_OK;
   if (!per_segment) {
     ProgPtr p;
-    rc = get_decode(c, present, data_only != 0, &p);
+    rc = get_decode(c, present, data_only != 0, &p, nullptr, required);
     if (rc) return rc;
     rc = do_decode(c, *p, L, nullptr, (uint32_t)nseg, st);
   } else {
@@ -1230,9 +1281,16 @@ int cec_reconstruct_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size
     //  * otherwise: one multi-pattern run-time launch per (chunk index, bucket), each segment's
     //    workgroup row reading its own pattern's chunk, so a batch where every segment has a
     //    different erasure map is still one full-grid launch.
-    std::string pkey(1, 'S');
-    pkey.reserve(nseg * n + 6);
-    for (size_t i = 0; i < nseg * n; ++i) pkey.push_back(present[i] ? 1 : 0);
+    std::string pkey(1, required ? 'T' : 'S');
+    pkey.reserve(nseg * n * (required ? 2 : 1) + 16);
+    if (!required) {
+      for (size_t i = 0; i < nseg * n; ++i) pkey.push_back(present[i] ? 1 : 0);
+    } else {  // per segment: n presence flags, then n required flags
+      for (size_t s = 0; s < nseg; ++s) {
+        for (int i = 0; i < n; ++i) pkey.push_back(present[s * n + i] ? 1 : 0);
+        for (int i = 0; i < n; ++i) pkey.push_back(required[s * n + i] ? 1 : 0);
+      }
+    }
     pkey.push_back(data_only ? 1 : 0);
     pkey.push_back(c->force_generic ? 1 : 0);
     const bool fdok = cec::fftdec_layout_ok(L);
@@ -1242,7 +1300,8 @@ int cec_reconstruct_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size
     for (int b = 0; b < 8; ++b) pkey.push_back((char)(shard_len >> (8 * b)));  // the split rule
     if (!c->ps || c->ps->key != pkey) {
       std::unique_ptr<PsPlan> plan;
-      rc = build_ps_plan(c, pkey, nseg, data_only != 0, &plan, false, fdok, shard_len);
+      rc = build_ps_plan(c, pkey, nseg, data_only != 0, &plan, false, fdok, shard_len,
+                         required != nullptr);
       if (rc) return rc;
       c->drop_plan();  // the old plan's arrays are retired: launches already enqueued keep them
       c->ps = std::move(plan);
@@ -1258,6 +1317,218 @@ int cec_reconstruct_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size
   int mrc = c->pool.mark(st);
   evict_decode(c);
   return rc ? rc : mrc;
+}
+
+int cec_reconstruct_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size_t nseg,
+                          size_t shard_len, const uint8_t* present, int per_segment,
+                          int data_only, void* hip_stream) {
+  return reconstruct_batch_impl(c, d_data, d_parity, nseg, shard_len, present, nullptr,
+                                per_segment, data_only, hip_stream);
+}
+
+int cec_reconstruct_some_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size_t nseg,
+                               size_t shard_len, const uint8_t* present, const uint8_t* required,
+                               int per_segment, void* hip_stream) {
+  if (!required) return set_err(CEC_EINVAL, "null");
+  return reconstruct_batch_impl(c, d_data, d_parity, nseg, shard_len, present, required,
+                                per_segment, 0, hip_stream);
+}
+
+int cec_decode_rows(int k, int m, const uint8_t* present, const uint8_t* required, uint8_t* rows,
+                    uint8_t* out_idx, int* nreq) {
+  if (!present || !required || !rows || !out_idx || !nreq) return set_err(CEC_EINVAL, "null");
+  if (k < 1 || m < 1 || k + m > cec::kMaxShards)
+    return set_err(CEC_EINVAL, "need k >= 1, m >= 1, k + m <= 256");
+  const int n = k + m;
+  auto E = std::make_unique<BigMat>();
+  auto a = std::make_unique<BigMat>();
+  auto ainv = std::make_unique<BigMat>();
+  auto work = std::make_unique<WorkMat>();
+  auto plan = std::make_unique<BigPlan>();
+  if (!cec::gf_encode_matrix(k, m, *E, *a, *ainv, *work))
+    return set_err(CEC_EINVAL, "singular Vandermonde top block");
+  uint8_t flags[cec::kMaxShards], rd[cec::kMaxShards];
+  for (int i = 0; i < n; ++i) flags[i] = present[i] ? 1 : 0;
+  if (!cec::survivor_set(k, m, flags, rd) ||
+      cec::gf_decode_plan_sys(k, m, flags, false, *E, *plan, *a, *ainv, *work, rd) != 0)
+    return set_err(CEC_ETOOFEW, "fewer than k shards present");
+  int w = 0;
+  for (int o = 0; o < plan->nout; ++o) {  // out_idx ascending, survivors in cec_survivors order
+    if (!required[plan->out_idx[o]]) continue;
+    out_idx[w] = plan->out_idx[o];
+    std::memcpy(rows + (size_t)w * k, plan->coef.v[o], k);
+    ++w;
+  }
+  *nreq = w;
+  return CEC_OK;
+}
+
+// The pointer-table calls. Everything is validated and every program resolved before the first
+// launch; the table is built on the host from the caller's arrays (which are not read after the
+// return), uploaded to a pool block on the codec's stream and complete before the launches, and
+// retired in stream order behind them.
+static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_t* const* dst,
+                                 size_t nseg, size_t shard_len, hipStream_t st) {
+  const int n = c->k + c->m, k = c->k;
+  struct Group {
+    ProgPtr prog;
+    std::vector<uint32_t> segs;
+  };
+  std::unordered_map<std::string, size_t> gidx;
+  std::vector<Group> groups;
+  struct Uploads {  // new patterns' images stay in flight until the one synchronisation below
+    hipStream_t st;
+    PinnedArena& arena;
+    ~Uploads() {
+      if (arena.busy()) (void)hipStreamSynchronize(st);
+      arena.reset();
+    }
+  } up{c->stream, c->arena};
+  std::string key(2 * (size_t)n, '\0');
+  uintptr_t bits = 0;  // OR of every address read or written: the alignment of the call
+  for (size_t s = 0; s < nseg; ++s) {
+    const uint8_t* const* sp = src + s * n;
+    uint8_t* const* dp = dst + s * n;
+    for (int i = 0; i < n; ++i) {
+      key[i] = sp[i] ? 1 : 0;
+      key[n + i] = !sp[i] && dp[i] ? 1 : 0;
+    }
+    auto it = gidx.find(key);
+    if (it == gidx.end()) {
+      const uint8_t* f = reinterpret_cast<const uint8_t*>(key.data());
+      ProgPtr p;
+      int rc = get_decode(c, f, false, &p, &up.arena, f + n);
+      if (rc) return rc;
+      it = gidx.emplace(key, groups.size()).first;
+      groups.push_back({p, {}});
+    }
+    Group& g = groups[it->second];
+    const Program& p = *g.prog;
+    if (!p.nout) continue;  // nothing wanted: no row, no work
+    for (int o = 0; o < p.nout; ++o) {
+      const uint8_t* d = dp[p.out_idx[o]];
+      bits |= (uintptr_t)d;
+      for (int j = 0; j < k; ++j)
+        if (d == sp[p.in_idx[j]])
+          return set_err(CEC_EINVAL, "a destination is a survivor of its own segment");
+    }
+    for (int j = 0; j < k; ++j) bits |= (uintptr_t)sp[p.in_idx[j]];
+    g.segs.push_back((uint32_t)s);
+  }
+  const bool vec_ok = (bits & 15) == 0;
+  // launches: RS(2,1) rows for the compile-time kernel; otherwise one launch per (kernel, bucket)
+  // over the rows of every pattern's chunk of that kind
+  struct Launch {
+    int kind;  // 0: RS(2,1) compile-time, 1: bit-plane (k_rtb's cases), 2: general
+    int nob;
+    uint32_t rs;
+    std::vector<uint64_t> rows;
+  };
+  std::vector<Launch> launches;
+  auto launch_of = [&](int kind, int nob, uint32_t rs) -> Launch& {
+    for (auto& l : launches)
+      if (l.kind == kind && l.nob == nob && l.rs == rs) return l;
+    launches.push_back({kind, nob, rs, {}});
+    return launches.back();
+  };
+  const bool ct21 = k == 2 && c->m == 1 && !c->force_generic;
+  for (const Group& g : groups) {
+    const Program& p = *g.prog;
+    if (!p.nout || g.segs.empty()) continue;
+    if (ct21) {  // one lost shard: p.single
+      Launch& l = launch_of(0, 1, 4);
+      for (uint32_t s : g.segs) {
+        l.rows.push_back((uint64_t)(uintptr_t)src[(size_t)s * n + p.in_idx[0]]);
+        l.rows.push_back((uint64_t)(uintptr_t)src[(size_t)s * n + p.in_idx[1]]);
+        l.rows.push_back((uint64_t)(uintptr_t)dst[(size_t)s * n + p.out_idx[0]]);
+        l.rows.push_back((uint64_t)p.out_idx[0]);
+      }
+      continue;
+    }
+    int o0 = 0;
+    for (const RtChunk& ch : p.chunks) {
+      // the cases k_rtb takes in the batch layout (launch_chunk): up to four outputs from four
+      // or more inputs
+      const bool rtb = c->opts.rt_mode == 3 || (c->opts.rt_mode == 0 && ch.nob <= 4 && ch.nin >= 4);
+      Launch& l = launch_of(rtb && ch.nob <= 4 ? 1 : 2, ch.nob, (uint32_t)(1 + ch.nin + ch.nob));
+      for (uint32_t s : g.segs) {
+        const size_t r0 = l.rows.size();
+        l.rows.resize(r0 + l.rs, 0);
+        uint64_t* r = l.rows.data() + r0;
+        r[0] = (uint64_t)(uintptr_t)ch.dev;
+        for (int j = 0; j < ch.nin; ++j) r[1 + j] = (uint64_t)(uintptr_t)src[(size_t)s * n + p.in_idx[j]];
+        for (int o = 0; o < ch.nout; ++o)
+          r[1 + ch.nin + o] = (uint64_t)(uintptr_t)dst[(size_t)s * n + p.out_idx[o0 + o]];
+      }
+      o0 += ch.nout;
+    }
+  }
+  size_t words = 0;
+  for (const auto& l : launches) words += l.rows.size();
+  int rc = CEC_OK;
+  if (words) {
+    std::vector<uint64_t> host;
+    host.reserve(words);
+    for (const auto& l : launches) host.insert(host.end(), l.rows.begin(), l.rows.end());
+    void* d = nullptr;
+    const size_t bytes = words * sizeof(uint64_t);
+    rc = c->pool.alloc(bytes, &d);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(d, host.data(), bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the programs' uploads too
+    if (e != hipSuccess) {
+      c->pool.retire(d, bytes);
+      return set_err(CEC_EHIP, std::string("table upload: ") + hipGetErrorString(e));
+    }
+    up.arena.reset();
+    const uint64_t* tab = static_cast<const uint64_t*>(d);
+    for (const auto& l : launches) {
+      const uint32_t nrows = (uint32_t)(l.rows.size() / l.rs);
+      if (l.kind == 0)
+        cec::launch_ptrs_rs21(tab, nrows, shard_len, vec_ok, st);
+      else if (l.kind != 1 || !cec::launch_ptrs_rtb(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st))
+        cec::launch_ptrs_rt(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st);
+      rc = check_launch();
+      if (rc) break;
+      tab += l.rows.size();
+    }
+    const int mrc = c->pool.mark(st);  // the table and the programs stay until these complete
+    c->pool.retire(d, bytes);
+    if (!rc) rc = mrc;
+  }
+  evict_decode(c);
+  return rc;
+}
+
+int cec_reconstruct_ptrs(cec_codec* c, const uint8_t* const* src, uint8_t* const* dst,
+                         size_t nseg, size_t shard_len, void* hip_stream) {
+  if (!c || (nseg && (!src || !dst))) return set_err(CEC_EINVAL, "null");
+  if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
+  if (nseg > 0xffffffffull) return set_err(CEC_EINVAL, "too many segments");
+  if (nseg == 0) return CEC_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  return reconstruct_ptrs_impl(c, src, dst, nseg, shard_len, pick_stream(c, hip_stream));
+}
+
+int cec_encode_ptrs(cec_codec* c, const uint8_t* const* d_data_ptrs, uint8_t* const* d_parity_ptrs,
+                    size_t nseg, size_t shard_len, void* hip_stream) {
+  if (!c || (nseg && (!d_data_ptrs || !d_parity_ptrs))) return set_err(CEC_EINVAL, "null");
+  if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
+  if (nseg > 0xffffffffull) return set_err(CEC_EINVAL, "too many segments");
+  if (nseg == 0) return CEC_OK;
+  const int n = c->k + c->m;
+  std::vector<const uint8_t*> src(nseg * n, nullptr);
+  std::vector<uint8_t*> dst(nseg * n, nullptr);
+  for (size_t s = 0; s < nseg; ++s) {
+    for (int i = 0; i < c->k; ++i)
+      if (!(src[s * n + i] = d_data_ptrs[s * c->k + i])) return set_err(CEC_EINVAL, "null shard");
+    for (int o = 0; o < c->m; ++o)
+      if (!(dst[s * n + c->k + o] = d_parity_ptrs[s * c->m + o]))
+        return set_err(CEC_EINVAL, "null shard");
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  return reconstruct_ptrs_impl(c, src.data(), dst.data(), nseg, shard_len,
+                               pick_stream(c, hip_stream));
 }
 
 int cec_reconstruct_partial_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size_t nseg,

@@ -135,9 +135,11 @@ inline bool survivor_set(int k, int m, const uint8_t* present, uint8_t* read) {
 // stages — cess_ec.cpp's host API and the multi-GPU gathers move only those). Every shard not
 // read is an erasure to the algorithm; the outputs are the shards not present (data_only: data
 // shards only). Returns false when more than 32 shards are unread (the caller reports ETOOFEW) or
-// there is nothing to write.
+// there is nothing to write. `want` (64 flags, optional) restricts the outputs to the flagged lost
+// shards (cec_reconstruct_some_batch): the transform and the syndromes are those of the full
+// rebuild, only the rows and the stores of the unwanted outputs go.
 inline bool fftdec_plan_m(const uint8_t* read, const uint8_t* present, bool data_only,
-                          FftDecPlan* out) {
+                          FftDecPlan* out, const uint8_t* want = nullptr) {
   uint32_t erd = 0, erp = 0;  // unread data / parity
   uint32_t lost_d = 0, lost_p = 0;  // not present (the outputs)
   for (int t = 0; t < 32; ++t) {
@@ -147,6 +149,14 @@ inline bool fftdec_plan_m(const uint8_t* read, const uint8_t* present, bool data
     if (!present[32 + t]) lost_p |= 1u << t;
   }
   if ((lost_d & ~erd) || (lost_p & ~erp)) return false;  // a read shard must be present
+  uint32_t want_d = ~0u, want_p = ~0u;
+  if (want) {
+    want_d = want_p = 0;
+    for (int t = 0; t < 32; ++t) {
+      if (want[t]) want_d |= 1u << t;
+      if (want[32 + t]) want_p |= 1u << t;
+    }
+  }
   const int nd = fdp::popc(erd), np = fdp::popc(erp);
   if (nd + np > 32 || nd + np == 0) return false;
   // A = the coset with fewer erasures (fewer syndrome rows); data on a tie
@@ -154,8 +164,10 @@ inline bool fftdec_plan_m(const uint8_t* read, const uint8_t* present, bool data
   const unsigned baseA = side ? 32u : 0u, baseB = side ? 0u : 32u;
   const uint32_t DA = side ? erp : erd, EB = side ? erd : erp;
   // outputs on A (within DA) and on B (within EB)
-  const uint32_t OA = (side ? lost_p : lost_d) & ~(data_only && side == 1 ? ~0u : 0u);
-  const uint32_t OB = (side ? lost_d : lost_p) & ~(data_only && side == 0 ? ~0u : 0u);
+  const uint32_t OA = (side ? lost_p & want_p : lost_d & want_d) &
+                      ~(data_only && side == 1 ? ~0u : 0u);
+  const uint32_t OB = (side ? lost_d & want_d : lost_p & want_p) &
+                      ~(data_only && side == 0 ? ~0u : 0u);
   const int d = fdp::popc(DA);
   // R: d present points of B packed into few slots: whole present slots first, then a lone
   // read position of a slot that is packed anyway (it holds an output), then any
@@ -297,9 +309,9 @@ struct FftDecDLayout {
 // Build the mode-D plan for RS(32,32) pattern `present` (64 flags) reading only the shards flagged
 // in `read` (present ones; see fftdec_plan_m): the locator's roots are the unread shards, the
 // outputs the shards not present. False when more than 32 shards are unread or there is nothing
-// to write.
+// to write. `want` (optional) restricts the outputs as in fftdec_plan_m.
 inline bool fftdec_plan_d(const uint8_t* read, const uint8_t* present, bool data_only,
-                          FftDecPlan* out) {
+                          FftDecPlan* out, const uint8_t* want = nullptr) {
   int ne = 0, nout = 0;
   uint8_t erased[64];
   for (int t = 0; t < 64; ++t) {
@@ -319,7 +331,7 @@ inline bool fftdec_plan_d(const uint8_t* read, const uint8_t* present, bool data
     const int sh = 8 * (t & 3);
     if (read[t]) {
       w[FftDecDLayout::kLam + (t >> 2)] |= (uint32_t)lam << sh;
-    } else if (!present[t] && !(data_only && t >= 32)) {
+    } else if (!present[t] && !(data_only && t >= 32) && (!want || want[t])) {
       w[FftDecDLayout::kDinv + (t >> 2)] |= (uint32_t)gf_inv(lam) << sh;
       ++nout;
     }

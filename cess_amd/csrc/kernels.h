@@ -125,6 +125,23 @@ bool launch_matvec_rth(const KernelOpts& o, const Layout& L, const uint32_t* chu
                        const uint32_t* const* per_seg, int nin_max, const uint32_t* seg_list,
                        uint32_t nseg, hipStream_t st);
 
+// Pointer-table addressing (scattered shards, cec_reconstruct_ptrs): `tab` holds `nrows` rows of
+// 64-bit words in HBM, one per workgroup row, the device addresses of a segment's inputs in
+// program order, then of its outputs, each `len` bytes. vec_ok: every address in the rows is
+// 16-byte aligned (else the byte path runs for the whole launch).
+// RS(2,1), compile-time coefficients: row = {input 0, input 1, output, case}, case 0 / 1 = rebuild
+// data fragment 0 / 1 from (the other data fragment, the parity), 2 = encode from (d0, d1).
+void launch_ptrs_rs21(const uint64_t* tab, uint32_t nrows, uint64_t len, bool vec_ok,
+                      hipStream_t st);
+// Run-time programs: row = {address of the segment's program chunk, its nin inputs, its nout
+// outputs}, rows `rs` words apart (rs >= 1 + nin + nout), every chunk of the launch of bucket
+// `nob`. _rtb: the bit-plane product for nob <= 4 (false, nothing launched, for a wider bucket);
+// _rt: the per-bit mask product for any bucket.
+bool launch_ptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
+                     bool vec_ok, hipStream_t st);
+void launch_ptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
+                    bool vec_ok, hipStream_t st);
+
 // SHA-256 of `n` equal-length buffers, written as 64 lowercase hex characters each into
 // `hex_out` (device, n * 64 bytes). If `ptrs` is null, buffer i is shard (i % nshards) of
 // segment (i / nshards) in layout L.

@@ -1648,4 +1648,311 @@ void launch_fill_splitmix(uint8_t* out, uint64_t seg_bytes, uint64_t nseg, uint6
                      seed);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Pointer-table addressing (cec_reconstruct_ptrs / cec_encode_ptrs)
+// ---------------------------------------------------------------------------------------------
+// Scattered shards: every workgroup row (blockIdx.y) owns one row of 64-bit words in a device
+// table, the addresses of its inputs in program order, then of its outputs. The row is read
+// through the constant address space like the program chunks, so the addresses arrive as
+// wave-uniform scalar loads ahead of the global loads, and they are turned into address_space(1)
+// pointers, not generic ones: the accesses stay global_load / global_store (a flat access counts
+// on lgkmcnt too and would serialise with the scalar reads, see shard_ptr_sel). The column bodies
+// are those of the in-layout kernels (ct_column_*, the k_rt and k_rtb products); only the
+// addressing differs. `vec_ok` is per call: every address of the table is 16-byte aligned.
+typedef const uint64_t __attribute__((address_space(4))) cu64;
+typedef uint8_t __attribute__((address_space(1))) gu8;
+
+__device__ __forceinline__ const cu64* tab_row(const uint64_t* tab, uint64_t row, uint32_t rs) {
+  return (const cu64*)(uintptr_t)tab + row * rs;
+}
+__device__ __forceinline__ gu8* gptr(uint64_t a) { return (gu8*)a; }
+
+template <bool NT, class TV>
+__device__ __forceinline__ TV gld(const gu8* p) {
+  typedef const TV __attribute__((address_space(1))) G;
+  if constexpr (NT) return __builtin_nontemporal_load((G*)p);
+  else return *(G*)p;
+}
+template <bool NT, class TV>
+__device__ __forceinline__ void gst(gu8* p, TV v) {
+  typedef TV __attribute__((address_space(1))) G;
+  if constexpr (NT) __builtin_nontemporal_store(v, (G*)p);
+  else *(G*)p = v;
+}
+
+// RS(2,1) with compile-time coefficients: row = {input 0, input 1, output, case}; case 0 / 1 =
+// the closed-form rebuild of data fragment 0 / 1 (inputs: the other data fragment, the parity),
+// 2 = the encode (inputs: d0, d1). One launch mixes the cases as k_ct_dec1_mixed21 does (a
+// wave-uniform branch); segments with nothing wanted have no row.
+template <class P, bool NT>
+__device__ __forceinline__ void ptr_tile21(gu8* i0, gu8* i1, gu8* o0, uint64_t len, int vec_ok) {
+  using TV = u32x4;
+  constexpr int VB = sizeof(TV);
+  if (vec_ok) {
+    const uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v < len / VB) {
+      const uint64_t off = v * VB;
+      auto ld = [&](auto J) CEC_AI {
+        if constexpr (decltype(J)::value == 0) return gld<NT, TV>(i0 + off);
+        else return gld<NT, TV>(i1 + off);
+      };
+      auto st = [&](auto, TV y) CEC_AI { gst<NT, TV>(o0 + off, y); };
+      if constexpr (Rs21Closed<P>::missing >= 0) ct_column_rs21<Rs21Closed<P>::missing, TV>(ld, st);
+      else if constexpr (use_horner<P>(1)) ct_column_horner<P, TV>(ld, st);
+      else ct_column_stream<P, 1, TV>(ld, st);
+    }
+    if (!(len % VB) || blockIdx.x != gridDim.x - 1) return;
+  }
+  // byte path: whole shard (vec_ok == 0, grid covers len) or the tail (last block)
+  const uint64_t i = vec_ok ? (len - len % VB) + threadIdx.x
+                            : (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= len) return;
+  auto ld = [&](auto J) CEC_AI -> uint32_t {
+    if constexpr (decltype(J)::value == 0) return i0[i];
+    else return i1[i];
+  };
+  auto st = [&](auto, uint32_t y) CEC_AI { o0[i] = (uint8_t)y; };
+  if constexpr (use_horner<P>(1)) ct_column_horner<P, uint32_t>(ld, st);
+  else ct_column_stream<P, 1, uint32_t>(ld, st);
+}
+
+template <bool NT>
+__global__ __launch_bounds__(256) void k_ptr21(const uint64_t* __restrict__ tab, uint32_t row0,
+                                               uint64_t len, int vec_ok) {
+  const cu64* __restrict__ row = tab_row(tab, row0 + blockIdx.y, 4);
+  // the whole row in one scalar load ahead of the case branch: the addresses are then one
+  // scalar-cache round trip from the first global load, not two
+  gu8* const i0 = gptr(row[0]);
+  gu8* const i1 = gptr(row[1]);
+  gu8* const o0 = gptr(row[2]);
+  const uint32_t e = (uint32_t)row[3];
+  if (e == 0) ptr_tile21<Dec1CT<2, 1, 0>, NT>(i0, i1, o0, len, vec_ok);
+  else if (e == 1) ptr_tile21<Dec1CT<2, 1, 1>, NT>(i0, i1, o0, len, vec_ok);
+  else if (e == 2) ptr_tile21<EncCT<2, 1>, NT>(i0, i1, o0, len, vec_ok);
+}
+
+// Run-time coefficients: row = {program chunk, nin inputs, nout outputs} in the chunk's order
+// (its in / out index arrays are not read: the row already is in program order), rows of a launch
+// `rs` words apart. k_rt's product (rt_accumulate) with input j addressed by position.
+template <int NOB, int U, class TV, class T, class LD>
+__device__ __forceinline__ void rt_accumulate_tab(T (&acc)[NOB][U], const cu32* __restrict__ P,
+                                                  LD ld) {
+  const uint32_t nin = P[0];
+  const cu32* __restrict__ hbs = P + 4 + 512;
+  const cu32* __restrict__ masks = P + kRtHeaderWords;
+  T cur[U], nxt[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) cur[u] = ld(0u, u);
+  for (uint32_t j = 0; j < nin; ++j) {
+    if (j + 1 < nin) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) nxt[u] = ld(j + 1, u);
+    }
+    const int hb = (int)hbs[j];
+    T p[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) p[u] = cur[u];
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      if (b > hb) break;  // wave-uniform: no higher coefficient bit in this column
+      if (b > 0) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) p[u] = xt(p[u]);
+      }
+      const cu32* __restrict__ mk = masks + (j * 8 + b) * NOB;
+#pragma unroll
+      for (int o = 0; o < NOB; ++o) {
+        const uint32_t m = mk[o];
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc[o][u] = bitop3_xand(acc[o][u], p[u], m);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+  }
+}
+
+// The general form (k_rt with table addressing): any output count up to the bucket NOB.
+template <int NOB, int U, class TV>
+__global__ __launch_bounds__(256) void k_ptrt(const uint64_t* __restrict__ tab, uint32_t row0,
+                                              uint32_t rs, uint64_t len, int vec_ok) {
+  const cu64* __restrict__ row = tab_row(tab, row0 + blockIdx.y, rs);
+  const cu32* __restrict__ P = as_const((const uint32_t*)(uintptr_t)row[0]);
+  const uint32_t nin = P[0], nout = P[1];
+  const cu64* __restrict__ in = row + 1;
+  const cu64* __restrict__ out = in + nin;
+  constexpr int VB = sizeof(TV);
+  if (vec_ok) {
+    const uint64_t nvec = len / VB;
+    const uint64_t base = (uint64_t)blockIdx.x * (256 * U) + threadIdx.x;
+    TV acc[NOB][U];
+#pragma unroll
+    for (int o = 0; o < NOB; ++o)
+#pragma unroll
+      for (int u = 0; u < U; ++u) acc[o][u] = TV(0);
+    auto ld = [&](uint32_t j, int u) CEC_AI -> TV {
+      const uint64_t v = base + u * 256;
+      if (v >= nvec) return TV(0);
+      return gld<false, TV>(gptr(in[j]) + v * VB);
+    };
+    rt_accumulate_tab<NOB, U, TV>(acc, P, ld);
+#pragma unroll
+    for (int o = 0; o < NOB; ++o) {
+      if (o < (int)nout) {
+        gu8* dst = gptr(out[o]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const uint64_t v = base + u * 256;
+          if (v < nvec) gst<false, TV>(dst + v * VB, acc[o][u]);
+        }
+      }
+    }
+    if (!(len % VB) || blockIdx.x != gridDim.x - 1) return;
+  }
+  // byte path: whole shard (vec_ok == 0, grid covers len) or the tail (last block)
+  const uint64_t i = vec_ok ? (len - len % VB) + threadIdx.x
+                            : (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= len) return;
+  uint32_t acc[NOB][1];
+#pragma unroll
+  for (int o = 0; o < NOB; ++o) acc[o][0] = 0;
+  auto ld = [&](uint32_t j, int) CEC_AI -> uint32_t { return gptr(in[j])[i]; };
+  rt_accumulate_tab<NOB, 1, uint32_t>(acc, P, ld);
+#pragma unroll
+  for (int o = 0; o < NOB; ++o)
+    if (o < (int)nout) gptr(out[o])[i] = (uint8_t)acc[o][0];
+}
+
+// The bit-plane form for few outputs (k_rtb with table addressing): 8 * NOB accumulators, the
+// inputs stream through a ring of PF columns.
+template <int NOB, class TV, int PF>
+__global__ __launch_bounds__(256) void k_ptrb(const uint64_t* __restrict__ tab, uint32_t row0,
+                                              uint32_t rs, uint64_t len, int vec_ok) {
+  const cu64* __restrict__ row = tab_row(tab, row0 + blockIdx.y, rs);
+  const cu32* __restrict__ P = as_const((const uint32_t*)(uintptr_t)row[0]);
+  const uint32_t nin = P[0], nout = P[1];
+  const cu64* __restrict__ in = row + 1;
+  const cu64* __restrict__ out = in + nin;
+  const cu32* __restrict__ masks = P + kRtHeaderWords;
+  auto fold = [&]<class T>(T (&t)[NOB][8], auto ld) CEC_AI {
+    T ring[PF];
+#pragma unroll
+    for (int q = 0; q < PF; ++q)
+      if (q < (int)nin) ring[q] = ld((uint32_t)q);
+    for (uint32_t j0 = 0; j0 < nin; j0 += PF) {
+#pragma unroll
+      for (int q = 0; q < PF; ++q) {
+        const uint32_t j = j0 + q;
+        if (j >= nin) break;  // wave-uniform
+        const T cur = ring[q];
+        if (j + PF < nin) ring[q] = ld(j + PF);
+        const cu32* __restrict__ mk = masks + j * 8 * NOB;
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+#pragma unroll
+          for (int o = 0; o < NOB; ++o) t[o][b] = bitop3_xand(t[o][b], cur, mk[b * NOB + o]);
+      }
+    }
+  };
+  auto horner = [&]<class T>(const T (&t)[8]) CEC_AI -> T {
+    T r = t[7];
+#pragma unroll
+    for (int b = 6; b >= 0; --b) r = xt(r) ^ t[b];
+    return r;
+  };
+  constexpr int VB = sizeof(TV);
+  if (vec_ok) {
+    const uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v < len / VB) {
+      TV t[NOB][8];
+#pragma unroll
+      for (int o = 0; o < NOB; ++o)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) t[o][b] = TV(0);
+      fold(t, [&](uint32_t j) CEC_AI { return gld<true, TV>(gptr(in[j]) + v * VB); });
+#pragma unroll
+      for (int o = 0; o < NOB; ++o)
+        if (o < (int)nout) gst<true, TV>(gptr(out[o]) + v * VB, horner(t[o]));
+    }
+    if (!(len % VB) || blockIdx.x != gridDim.x - 1) return;
+  }
+  // byte path: whole shard (vec_ok == 0, grid covers len) or the tail (last block)
+  const uint64_t i = vec_ok ? (len - len % VB) + threadIdx.x
+                            : (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= len) return;
+  uint32_t t[NOB][8];
+#pragma unroll
+  for (int o = 0; o < NOB; ++o)
+#pragma unroll
+    for (int b = 0; b < 8; ++b) t[o][b] = 0;
+  fold(t, [&](uint32_t j) CEC_AI -> uint32_t { return gptr(in[j])[i]; });
+#pragma unroll
+  for (int o = 0; o < NOB; ++o)
+    if (o < (int)nout) gptr(out[o])[i] = (uint8_t)horner(t[o]);
+}
+
+namespace {
+template <int NOB, int U, class TV>
+void run_ptrt(const uint64_t* tab, uint32_t nrows, uint32_t rs, uint64_t len, int vec_ok,
+              hipStream_t st) {
+  uint64_t gx = vec_ok ? (len / sizeof(TV) + 256 * U - 1) / (256 * U) : (len + 255) / 256;
+  if (gx == 0) gx = 1;
+  for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
+    hipLaunchKernelGGL((k_ptrt<NOB, U, TV>), dim3((unsigned)gx, ny), dim3(256), 0, st, tab, r0, rs,
+                       len, vec_ok);
+  });
+}
+template <int NOB, class TV, int PF>
+void run_ptrb(const uint64_t* tab, uint32_t nrows, uint32_t rs, uint64_t len, int vec_ok,
+              hipStream_t st) {
+  uint64_t gx = vec_ok ? (len / sizeof(TV) + 255) / 256 : (len + 255) / 256;
+  if (gx == 0) gx = 1;
+  for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
+    hipLaunchKernelGGL((k_ptrb<NOB, TV, PF>), dim3((unsigned)gx, ny), dim3(256), 0, st, tab, r0, rs,
+                       len, vec_ok);
+  });
+}
+}  // namespace
+
+void launch_ptrs_rs21(const uint64_t* tab, uint32_t nrows, uint64_t len, bool vec_ok,
+                      hipStream_t st) {
+  uint64_t gx = vec_ok ? (len / 16 + 255) / 256 : (len + 255) / 256;
+  if (gx == 0) gx = 1;
+  for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
+    hipLaunchKernelGGL((k_ptr21<true>), dim3((unsigned)gx, ny), dim3(256), 0, st, tab, r0, len,
+                       vec_ok ? 1 : 0);
+  });
+}
+
+bool launch_ptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
+                     bool vec_ok, hipStream_t st) {
+  const int v = vec_ok ? 1 : 0;
+  switch (nob) {  // the column widths and ring depths of launch_matvec_rtb
+    case 1: run_ptrb<1, u32x2, 4>(tab, nrows, rs, len, v, st); return true;
+    case 2: run_ptrb<2, u32x2, 4>(tab, nrows, rs, len, v, st); return true;
+    case 3: run_ptrb<3, u32x2, 4>(tab, nrows, rs, len, v, st); return true;
+    case 4: run_ptrb<4, u32x2, 8>(tab, nrows, rs, len, v, st); return true;
+  }
+  return false;
+}
+
+void launch_ptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
+                    bool vec_ok, hipStream_t st) {
+  const int v = vec_ok ? 1 : 0;
+  switch (nob) {  // the column widths of launch_matvec_rt
+    case 1: run_ptrt<1, 1, u32x4>(tab, nrows, rs, len, v, st); break;
+    case 2: run_ptrt<2, 1, u32x4>(tab, nrows, rs, len, v, st); break;
+    case 3: run_ptrt<3, 1, u32x4>(tab, nrows, rs, len, v, st); break;
+    case 4: run_ptrt<4, 1, u32x4>(tab, nrows, rs, len, v, st); break;
+    case 5: run_ptrt<5, 1, u32x4>(tab, nrows, rs, len, v, st); break;
+    case 6: run_ptrt<6, 1, u32x4>(tab, nrows, rs, len, v, st); break;
+    case 7: run_ptrt<7, 1, u32x2>(tab, nrows, rs, len, v, st); break;
+    case 8: run_ptrt<8, 1, u32x2>(tab, nrows, rs, len, v, st); break;
+    case 12: run_ptrt<12, 1, u32x2>(tab, nrows, rs, len, v, st); break;
+    case 16: run_ptrt<16, 1, uint32_t>(tab, nrows, rs, len, v, st); break;
+    case 24: run_ptrt<24, 1, uint32_t>(tab, nrows, rs, len, v, st); break;
+    default: run_ptrt<32, 1, uint32_t>(tab, nrows, rs, len, v, st); break;
+  }
+}
+
 }  // namespace cec

@@ -66,6 +66,10 @@ class ErrReconstructRequired(CecError, ValueError):
     """reconstruction required as one or more required data shards are nil"""
 
 
+class ErrInvalidInput(CecError, ValueError):
+    """invalid input"""
+
+
 class HipError(CecError, RuntimeError):
     code = _lib.CEC_EHIP
 
@@ -244,6 +248,115 @@ class Encoder:
         """Recreate only missing data shards."""
         self._reconstruct(shards, data_only=True)
 
+    def _required_flags(self, required) -> List[bool]:
+        """klauspost's `required` argument: Shards flags, or DataShards flags (data shards only)."""
+        req = [bool(r) for r in required]
+        if len(req) == self.DataShards:
+            req += [False] * self.ParityShards
+        if len(req) != self.Shards:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        return req
+
+    def ReconstructSome(self, shards: List, required: Sequence) -> None:
+        """klauspost ReconstructSome: recreate only the missing shards flagged in `required`
+        (len Shards, or len DataShards to ask for data shards only). Missing shards that were not
+        asked for stay None; flags on present shards are ignored. The k survivors are staged in
+        HBM as separate buffers and rebuilt by cec_reconstruct_ptrs."""
+        if len(shards) != self.Shards:
+            raise ErrTooFewShards(ErrTooFewShards.__doc__)
+        req = self._required_flags(required)
+        size = self._check_shards(shards, nil_ok=True)
+        present = [_present(s) for s in shards]
+        want = [i for i in range(self.Shards) if req[i] and not present[i]]
+        if not want:
+            return
+        if sum(present) < self.DataShards:
+            raise ErrTooFewShards(ErrTooFewShards.__doc__)
+        import torch
+        dev = torch.device("cuda", self.device)
+        flags = (c_uint8 * self.Shards)(*[1 if p else 0 for p in present])
+        surv = (c_uint8 * self.DataShards)()
+        check(self._lib.cec_survivors(self.DataShards, self.ParityShards, flags, surv),
+              "ReconstructSome")
+        d_shards: List = [None] * self.Shards
+        for i in surv:
+            d_shards[i] = torch.from_numpy(_as_u8(shards[i])).to(dev)
+        self.ReconstructDevice(d_shards, [i in want for i in range(self.Shards)])
+        for i in want:
+            shards[i] = d_shards[i].cpu().numpy()
+
+    def EncodeDevice(self, shards: Sequence, stream=None) -> None:
+        """Encode one segment whose k + m shards are separate 1-D uint8 device tensors: the m
+        parity tensors are written (cec_encode_ptrs). Enqueued on `stream` (default: torch's
+        current stream)."""
+        if len(shards) != self.Shards:
+            raise ErrTooFewShards(ErrTooFewShards.__doc__)
+        size = self._check_device_shards(shards)
+        if self.ParityShards == 0:
+            return
+        k = self.DataShards
+        data = (c_void_p * k)(*[_dev_ptr(t) for t in shards[:k]])
+        par = (c_void_p * self.ParityShards)(*[_dev_ptr(t) for t in shards[k:]])
+        check(self._lib.cec_encode_ptrs(self._h, data, par, 1, size,
+                                        self._device_stream(stream)), "EncodeDevice")
+
+    def ReconstructDevice(self, shards: List, required=None, out=None, stream=None) -> None:
+        """Rebuild missing shards of one segment held as a list of k + m 1-D uint8 device tensors
+        (None = absent) without packing them into one buffer (cec_reconstruct_ptrs). `required`
+        (klauspost's flags, see ReconstructSome) limits the rebuild to the flagged missing shards;
+        None rebuilds every missing shard. Wanted shards are allocated, or taken from `out` (a
+        list or {index: tensor} of device tensors of the shard length), and put into `shards`.
+        Enqueued on `stream` (default: torch's current stream)."""
+        import torch
+        if len(shards) != self.Shards:
+            raise ErrTooFewShards(ErrTooFewShards.__doc__)
+        size = self._check_device_shards([s for s in shards if s is not None])
+        req = [True] * self.Shards if required is None else self._required_flags(required)
+        want = [i for i in range(self.Shards) if shards[i] is None and req[i]]
+        if not want:
+            return
+        if sum(s is not None for s in shards) < self.DataShards:
+            raise ErrTooFewShards(ErrTooFewShards.__doc__)
+        dev = torch.device("cuda", self.device)
+        outs = {}
+        for i in want:
+            t = None
+            if out is not None:
+                t = out.get(i) if isinstance(out, dict) else out[i]
+            if t is None:
+                t = torch.empty(size, dtype=torch.uint8, device=dev)
+            elif t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != size:
+                raise ErrShardSize(ErrShardSize.__doc__)
+            outs[i] = t
+        src = (c_void_p * self.Shards)(*[None if s is None else _dev_ptr(s) for s in shards])
+        dst = (c_void_p * self.Shards)(*[_dev_ptr(outs[i]) if i in outs else None
+                                         for i in range(self.Shards)])
+        check(self._lib.cec_reconstruct_ptrs(self._h, src, dst, 1, size,
+                                             self._device_stream(stream)), "ReconstructDevice")
+        for i, t in outs.items():
+            shards[i] = t
+
+    def _check_device_shards(self, tensors) -> int:
+        import torch
+        size = 0
+        for t in tensors:
+            if t.dtype != torch.uint8 or t.dim() != 1:
+                raise TypeError("device shards must be 1-D uint8 tensors")
+            if t.numel() == 0:
+                raise ErrShardNoData(ErrShardNoData.__doc__)
+            if size and t.numel() != size:
+                raise ErrShardSize(ErrShardSize.__doc__)
+            size = t.numel()
+        if size == 0:
+            raise ErrShardNoData(ErrShardNoData.__doc__)
+        return size
+
+    def _device_stream(self, stream):
+        if stream is not None:
+            return _stream_handle(stream)
+        import torch
+        return torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+
     def Split(self, data) -> List[np.ndarray]:
         """Split data into k equal shards (last zero padded) plus m zeroed parity shards."""
         src = _as_u8(data) if not isinstance(data, bytes) else np.frombuffer(data, np.uint8)
@@ -292,6 +405,24 @@ class Encoder:
             p.ctypes.data_as(POINTER(c_uint8)), per_segment, 1 if data_only else 0,
             _stream_handle(stream)), "ReconstructBatch")
 
+    def ReconstructSomeBatch(self, d_data, d_parity, nseg: int, shard_len: int, present,
+                             required, stream=None) -> None:
+        """ReconstructBatch for the missing shards flagged in `required` only (the same shape as
+        `present`: n flags, or nseg x n); other missing shards' memory is left as it is."""
+        p = np.ascontiguousarray(np.asarray(present, dtype=np.uint8))
+        r = np.ascontiguousarray(np.asarray(required, dtype=np.uint8))
+        per_segment = 1 if p.ndim == 2 else 0
+        if per_segment and p.shape != (nseg, self.Shards):
+            raise ValueError("present must be (nseg, k+m)")
+        if not per_segment and p.shape != (self.Shards,):
+            raise ValueError("present must have k+m flags")
+        if r.shape != p.shape:
+            raise ValueError("required must have the shape of present")
+        check(self._lib.cec_reconstruct_some_batch(
+            self._h, _dev_ptr(d_data), _dev_ptr(d_parity), nseg, shard_len,
+            p.ctypes.data_as(POINTER(c_uint8)), r.ctypes.data_as(POINTER(c_uint8)), per_segment,
+            _stream_handle(stream)), "ReconstructSomeBatch")
+
     def ReconstructPartialBatch(self, d_data, d_parity, nseg: int, shard_len: int, present,
                                 held, data_only: bool = False, stream=None) -> None:
         """Partial rebuild (cec_reconstruct_partial_batch): every missing shard of segment s gets
@@ -338,6 +469,25 @@ class Encoder:
 def New(data_shards: int, parity_shards: int, device: int = 0, tuning: bool = False) -> Encoder:
     """klauspost reedsolomon.New(dataShards, parityShards) on a GPU."""
     return Encoder(data_shards, parity_shards, device, tuning)
+
+
+def decode_rows(data_shards: int, parity_shards: int, present, required):
+    """Host only (cec_decode_rows): the decode rows of the lost shards of pattern `present` flagged
+    in `required` (k+m flags each). Returns (shard indices ascending, rows [nreq][k] uint8 over the
+    survivors in cec_survivors order)."""
+    n = data_shards + parity_shards
+    p = np.ascontiguousarray(np.asarray(present, dtype=np.uint8))
+    r = np.ascontiguousarray(np.asarray(required, dtype=np.uint8))
+    if p.shape != (n,) or r.shape != (n,):
+        raise ValueError("present and required must have k+m flags")
+    rows = np.zeros((n, data_shards), dtype=np.uint8)
+    idx = np.zeros(n, dtype=np.uint8)
+    nreq = c_int(0)
+    u8p = POINTER(c_uint8)
+    check(_lib.load().cec_decode_rows(data_shards, parity_shards, p.ctypes.data_as(u8p),
+                                      r.ctypes.data_as(u8p), rows.ctypes.data_as(u8p),
+                                      idx.ctypes.data_as(u8p), byref(nreq)), "decode_rows")
+    return idx[:nreq.value].copy(), rows[:nreq.value].copy()
 
 
 def fill_synthetic(d_out, seg_bytes: int, nseg: int, seg0: int, seed: int, stream=None) -> None:

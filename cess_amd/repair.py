@@ -50,10 +50,8 @@ def repair_fragment(enc: Encoder, survivors: Dict[int, np.ndarray], index: int,
     for i, b in survivors.items():
         if i != index:
             shards[i] = np.ascontiguousarray(b, dtype=np.uint8)
-    if index < enc.DataShards:
-        enc.ReconstructData(shards)
-    else:
-        enc.Reconstruct(shards)
+    # the order names one fragment: rebuild that one, not every absent fragment of the segment
+    enc.ReconstructSome(shards, [i == index for i in range(n)])
     out = shards[index]
     if expected_hash is not None:
         got = hashlib.sha256(out).hexdigest().encode()

@@ -90,8 +90,10 @@ int cec_verify(cec_codec* codec, uint8_t* const* shards, size_t shard_len, int* 
  * one uncaptured call of the same shape: cec_encode_batch of RS(2,1) and RS(32,32), and
  * cec_reconstruct_batch of RS(2,1) with one pattern (per_segment = 0). Every other rebuild reads
  * a decode program from the codec's cache, which may evict it while a graph still points at it:
- * do not capture those. A single 16 MiB RS(2,1) segment's encode + three rebuilds: 29.5 us
- * eagerly, 24.8 us as one graph (profiles/r05/graph_probe.log). */
+ * do not capture those, nor cec_reconstruct_some_batch, nor the pointer-table calls
+ * (cec_reconstruct_ptrs, cec_encode_ptrs: their kernels read a codec-owned table that is retired
+ * once the call's launches complete). A single 16 MiB RS(2,1) segment's encode + three rebuilds:
+ * 29.5 us eagerly, 24.8 us as one graph (profiles/r05/graph_probe.log). */
 int cec_encode_batch(cec_codec* codec, const uint8_t* d_data, uint8_t* d_parity, size_t nseg,
                      size_t shard_len, void* hip_stream);
 /* Rebuild missing shards in place in the same layout. `present` is a host array of k+m flags
@@ -101,6 +103,52 @@ int cec_encode_batch(cec_codec* codec, const uint8_t* d_data, uint8_t* d_parity,
 int cec_reconstruct_batch(cec_codec* codec, uint8_t* d_data, uint8_t* d_parity, size_t nseg,
                           size_t shard_len, const uint8_t* present, int per_segment,
                           int data_only, void* hip_stream);
+/* Host only. Rows of the decode of `present` (k+m flags) for the shards flagged in `required`
+ * (k+m flags; flags of present shards are ignored): *nreq outputs, out_idx[r] their shard indices
+ * ascending, rows[r*k + j] the coefficient of survivor j (cec_survivors order).
+ * CEC_ETOOFEW below k present. */
+int cec_decode_rows(int k, int m, const uint8_t* present, const uint8_t* required,
+                    uint8_t* rows, uint8_t* out_idx, int* nreq);
+/* ReconstructSome on the batch layout: as cec_reconstruct_batch, but only missing shards flagged
+ * in `required` (same shape as `present`) are written; other missing shards' memory is untouched.
+ * The restoral flow's case: an order names one fragment, and rebuilding one lost fragment of a
+ * wide segment costs less than rebuilding all of them. The survivors read are those of the
+ * pattern (cec_survivors), whatever is required. Decode programs share the codec's LRU cache
+ * under a key that also holds the required mask; a mask naming every missing shard is the full
+ * rebuild's entry. RS(32,32) goes through the same cost model and FFT-domain decoders with the
+ * real output count. */
+int cec_reconstruct_some_batch(cec_codec* codec, uint8_t* d_data, uint8_t* d_parity, size_t nseg,
+                               size_t shard_len, const uint8_t* present, const uint8_t* required,
+                               int per_segment, void* hip_stream);
+/* Scattered shards. src, dst: HOST arrays of nseg*(k+m) DEVICE pointers. src[s*n+i] NULL = shard i
+ * of segment s is absent. dst[s*n+i] non-NULL = write shard i of segment s there (shard_len
+ * bytes); dst entries of present shards are ignored.
+ *  - Reads: only the k survivors cec_survivors names for each segment's pattern are read.
+ *  - Writes: nothing but the shard_len bytes at each wanted dst is written. A segment with no
+ *    wanted output costs nothing (it gets no workgroup, and its shards are not counted).
+ *  - Validation: all segments are validated before anything is enqueued; on CEC_ETOOFEW,
+ *    CEC_ESHARDLEN or CEC_EINVAL no byte is written. A NULL array, or a dst equal to a survivor
+ *    address of its own segment, gives CEC_EINVAL. nseg == 0 is a no-op that returns CEC_OK.
+ *  - Pointer arrays: the library copies them into a device table before returning, so both
+ *    belong to the caller again on return. The work itself is enqueued on hip_stream and not
+ *    waited for.
+ *  - Alignment: any alignment and any shard_len >= 1 is correct. When every address the call
+ *    reads or writes is 16-byte aligned the kernels take 16-byte (or 8-byte) columns, otherwise
+ *    the whole call runs byte-wise (the fallback is per call).
+ *  - HIP graph capture: not capturable. The kernels read the codec-owned pointer table and, for
+ *    every code but RS(2,1), decode programs from the codec's cache (see the note above).
+ * Every geometry runs table-addressed kernels: RS(2,1) the compile-time closed forms (mixed
+ * patterns in one launch), otherwise the run-time bit-plane kernel for up to four outputs from
+ * four or more inputs and the run-time mask kernel for the rest, RS(32,32) included: its
+ * FFT-domain decoders address a coset through one buffer resource with 32-bit offsets and cannot
+ * scatter. */
+int cec_reconstruct_ptrs(cec_codec* codec, const uint8_t* const* src, uint8_t* const* dst,
+                         size_t nseg, size_t shard_len, void* hip_stream);
+/* Encode = the above with the k data shards as src and the m parity buffers as dst:
+ * d_data_ptrs[s*k+i], d_parity_ptrs[s*m+o] (host arrays of device pointers, none NULL). */
+int cec_encode_ptrs(cec_codec* codec, const uint8_t* const* d_data_ptrs,
+                    uint8_t* const* d_parity_ptrs, size_t nseg, size_t shard_len,
+                    void* hip_stream);
 /* Partial rebuild (the partial-product exchange of a multi-GPU degraded read):
  * like cec_reconstruct_batch with per-segment patterns (present: nseg*(k+m) flags; survivors =
  * cec_survivors of each segment's pattern), but every missing shard receives only the
@@ -547,8 +595,10 @@ int cec_set_option(cec_codec* codec, int option, int value);
 #define CEC_STAT_RETIRED_PENDING 2 /* device blocks retired but possibly still read by queued
                                       kernels (released once those complete) */
 #define CEC_STAT_POOL_BYTES 3      /* HBM held by the codec's block pool (programs, plans, small
-                                      scratch); batch-sized scratch is stream-ordered and is not
-                                      held after the call's launches complete */
+                                      scratch, the pointer tables of cec_reconstruct_ptrs: 8 bytes
+                                      per address, reused call after call); batch-sized scratch is
+                                      stream-ordered and is not held after the call's launches
+                                      complete */
 #define CEC_STAT_FFTDEC_SEGMENTS 4 /* segments rebuilt by the RS(32,32) FFT-domain decoders so far
                                       (the rest of a rebuild ran the run-time matrix kernels) */
 #define CEC_STAT_FFTDEC_D_SEGMENTS 5 /* of those, segments rebuilt by the formal-derivative decoder */

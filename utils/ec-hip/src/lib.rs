@@ -154,6 +154,18 @@ pub mod sys {
                                      nseg: usize, shard_len: usize, present: *const u8,
                                      per_segment: c_int, data_only: c_int,
                                      stream: *mut c_void) -> c_int;
+        pub fn cec_decode_rows(k: c_int, m: c_int, present: *const u8, required: *const u8,
+                               rows: *mut u8, out_idx: *mut u8, nreq: *mut c_int) -> c_int;
+        pub fn cec_reconstruct_some_batch(c: *mut cec_codec, d_data: *mut u8, d_parity: *mut u8,
+                                          nseg: usize, shard_len: usize, present: *const u8,
+                                          required: *const u8, per_segment: c_int,
+                                          stream: *mut c_void) -> c_int;
+        pub fn cec_reconstruct_ptrs(c: *mut cec_codec, src: *const *const u8,
+                                    dst: *const *mut u8, nseg: usize, shard_len: usize,
+                                    stream: *mut c_void) -> c_int;
+        pub fn cec_encode_ptrs(c: *mut cec_codec, d_data_ptrs: *const *const u8,
+                               d_parity_ptrs: *const *mut u8, nseg: usize, shard_len: usize,
+                               stream: *mut c_void) -> c_int;
         pub fn cec_reconstruct_partial_batch(c: *mut cec_codec, d_data: *mut u8,
                                              d_parity: *mut u8, nseg: usize, shard_len: usize,
                                              present: *const u8, held: *const u8,
@@ -332,6 +344,7 @@ impl Drop for DistGroup<'_> {
     }
 }
 
+pub const CEC_EINVAL: c_int = -1;
 pub const CEC_ETOOFEW: c_int = -2;
 pub const CEC_ESHARDLEN: c_int = -3;
 pub const CEC_ESEGCOUNT: c_int = -9;
@@ -444,6 +457,43 @@ impl ReedSolomon {
     /// Recreate only the missing data shards.
     pub fn reconstruct_data(&self, shards: &mut [Option<Vec<u8>>]) -> Result<(), Error> {
         self.reconstruct_inner(shards, true)
+    }
+
+    /// Scattered device shards (`cec_reconstruct_ptrs`): `src` and `dst` hold `nseg * (k + m)`
+    /// device addresses, segment by segment; a null `src` entry is an absent shard, a non-null
+    /// `dst` entry of an absent shard asks for it there. Enqueued on `stream` (null: the HIP null
+    /// stream) and not waited for; both slices may be reused as soon as the call returns.
+    ///
+    /// # Safety
+    /// Every non-null address must be device memory of `shard_len` bytes on the codec's GPU that
+    /// stays valid until the stream has passed the call's work.
+    pub unsafe fn reconstruct_device(&self, src: &[*const u8], dst: &[*mut u8], shard_len: usize,
+                                     stream: *mut c_void) -> Result<(), Error> {
+        let n = self.k + self.m;
+        if src.len() != dst.len() || src.len() % n != 0 {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        check(cec_reconstruct_ptrs(self.c, src.as_ptr(), dst.as_ptr(), src.len() / n, shard_len,
+                                   stream))
+    }
+
+    /// The decode rows of the `required` lost shards of pattern `present` (`cec_decode_rows`):
+    /// (shard indices ascending, one row of k coefficients over `cec_survivors` each).
+    pub fn decode_rows(&self, present: &[u8], required: &[u8]) -> Result<(Vec<u8>, Vec<u8>), Error> {
+        let n = self.k + self.m;
+        if present.len() != n || required.len() != n {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        let mut rows = vec![0u8; n * self.k];
+        let mut idx = vec![0u8; n];
+        let mut nreq: c_int = 0;
+        check(unsafe {
+            cec_decode_rows(self.k as c_int, self.m as c_int, present.as_ptr(), required.as_ptr(),
+                            rows.as_mut_ptr(), idx.as_mut_ptr(), &mut nreq)
+        })?;
+        idx.truncate(nreq as usize);
+        rows.truncate(nreq as usize * self.k);
+        Ok((idx, rows))
     }
 }
 
