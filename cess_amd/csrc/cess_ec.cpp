@@ -1622,6 +1622,85 @@ int cec_xor_batch(uint8_t* d_dst, const uint8_t* d_src, size_t nsrc, size_t src_
   return check_launch();
 }
 
+// ---- parity accumulation (EncodeIdx, Update; acc.hip) ----------------------------------------
+
+namespace {
+
+// Whether any of the n reads [a + s * stride, a + s * stride + len), s < n, meets [p, p + plen).
+bool reads_meet(const uint8_t* a, size_t stride, size_t n, size_t len, const uint8_t* p,
+                size_t plen) {
+  typedef unsigned __int128 u128;
+  const u128 A = (uintptr_t)a, P = (uintptr_t)p;
+  u128 s = 0;  // the first read that ends past p
+  if (A + len <= P) {
+    if (stride == 0) return false;
+    s = (P - (A + len)) / stride + 1;
+  }
+  return s < n && A + s * stride < P + plen;
+}
+
+// Column idx of the parity rows of E: coef[o] = E[k + o][idx].
+void parity_column(const cec_codec* c, int idx, uint8_t* coef) {
+  for (int o = 0; o < c->m; ++o) coef[o] = c->E->v[c->k + o][idx];
+}
+
+int check_acc_shape(size_t nseg, size_t shard_len) {
+  if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
+  if (nseg > 0xffffffffull) return set_err(CEC_EINVAL, "too many segments");
+  if ((shard_len + 255) / 256 > 0x7fffffffull)
+    return set_err(CEC_EINVAL, "shard_len too large (> 512 GiB)");
+  return CEC_OK;
+}
+
+}  // namespace
+
+int cec_encode_idx_batch(cec_codec* c, const uint8_t* d_shard, size_t shard_seg_stride, int idx,
+                         uint8_t* d_parity, size_t nseg, size_t shard_len, int accumulate,
+                         void* hip_stream) {
+  if (!c || (nseg && (!d_shard || !d_parity))) return set_err(CEC_EINVAL, "null");
+  if (idx < 0 || idx >= c->k) return set_err(CEC_EINVAL, "data shard index out of range");
+  int rc = check_acc_shape(nseg, shard_len);
+  if (rc) return rc;
+  if (nseg > 1 && shard_seg_stride < shard_len)
+    return set_err(CEC_EINVAL, "shard_seg_stride < shard_len: shards overlap");
+  if (nseg == 0) return CEC_OK;
+  if (reads_meet(d_shard, shard_seg_stride, nseg, shard_len, d_parity,
+                 nseg * (size_t)c->m * shard_len))
+    return set_err(CEC_EINVAL, "the shard overlaps the parity");
+  HIP_TRY(hipSetDevice(c->device));
+  uint8_t coef[cec::kMaxShards];
+  parity_column(c, idx, coef);
+  const uint32_t slot = 0;
+  cec::launch_acc(d_shard, nullptr, shard_seg_stride, 0, d_parity, (uint64_t)c->m * shard_len,
+                  shard_len, shard_len, &slot, coef, 1, c->m, accumulate != 0, nseg,
+                  pick_stream(c, hip_stream));
+  return check_launch();
+}
+
+int cec_update_batch(cec_codec* c, const uint8_t* d_old, const uint8_t* d_new, uint8_t* d_parity,
+                     size_t nseg, size_t shard_len, const uint8_t* changed, void* hip_stream) {
+  if (!c || !changed || (nseg && (!d_old || !d_new || !d_parity)))
+    return set_err(CEC_EINVAL, "null");
+  int rc = check_acc_shape(nseg, shard_len);
+  if (rc) return rc;
+  std::vector<uint32_t> slots;
+  for (int j = 0; j < c->k; ++j)
+    if (changed[j]) slots.push_back((uint32_t)j);
+  if (nseg == 0 || slots.empty()) return CEC_OK;
+  const size_t seg_stride = (size_t)c->k * shard_len, par_bytes = nseg * (size_t)c->m * shard_len;
+  for (uint32_t j : slots)
+    if (reads_meet(d_old + j * shard_len, seg_stride, nseg, shard_len, d_parity, par_bytes) ||
+        reads_meet(d_new + j * shard_len, seg_stride, nseg, shard_len, d_parity, par_bytes))
+      return set_err(CEC_EINVAL, "a changed shard overlaps the parity");
+  HIP_TRY(hipSetDevice(c->device));
+  std::vector<uint8_t> coef(slots.size() * c->m);
+  for (size_t i = 0; i < slots.size(); ++i) parity_column(c, (int)slots[i], &coef[i * c->m]);
+  cec::launch_acc(d_old, d_new, seg_stride, shard_len, d_parity, (uint64_t)c->m * shard_len,
+                  shard_len, shard_len, slots.data(), coef.data(), (int)slots.size(), c->m, true,
+                  nseg, pick_stream(c, hip_stream));
+  return check_launch();
+}
+
 int cec_sha256_batch(cec_codec* c, const uint8_t* d_data, const uint8_t* d_parity, size_t nseg,
                      size_t shard_len, uint8_t* d_hex, void* hip_stream) {
   if (!c || !d_hex || (nseg && !d_data)) return set_err(CEC_EINVAL, "null");
@@ -1850,6 +1929,83 @@ int cec_verify(cec_codec* c, uint8_t* const* shards, size_t shard_len, int* ok) 
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (std::memcmp(par.data(), shards[c->k + o], shard_len) != 0) *ok = 0;
   }
+  return CEC_OK;
+}
+
+// Stages only what is read: [the shard][m parity shards], shards at stride pad256(len).
+int cec_encode_idx(cec_codec* c, const uint8_t* data_shard, int idx, uint8_t* const* parity,
+                   size_t shard_len) {
+  if (!c || !data_shard || !parity) return set_err(CEC_EINVAL, "null");
+  if (idx < 0 || idx >= c->k) return set_err(CEC_EINVAL, "data shard index out of range");
+  int rc = check_acc_shape(1, shard_len);
+  if (rc) return rc;
+  for (int o = 0; o < c->m; ++o)
+    if (!parity[o]) return set_err(CEC_EINVAL, "null parity shard");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t stride = pad256(shard_len);
+  rc = ensure(&c->stage, &c->stage_bytes, stride * (1 + (size_t)c->m), c->stream);
+  if (rc) return rc;
+  uint8_t* d_par = c->stage + stride;
+  HIP_TRY(hipMemcpyAsync(c->stage, data_shard, shard_len, hipMemcpyHostToDevice, c->stream));
+  for (int o = 0; o < c->m; ++o)
+    HIP_TRY(hipMemcpyAsync(d_par + o * stride, parity[o], shard_len, hipMemcpyHostToDevice,
+                           c->stream));
+  uint8_t coef[cec::kMaxShards];
+  parity_column(c, idx, coef);
+  const uint32_t slot = 0;
+  cec::launch_acc(c->stage, nullptr, 0, 0, d_par, 0, stride, shard_len, &slot, coef, 1, c->m, true,
+                  1, c->stream);
+  rc = check_launch();
+  if (rc) return rc;
+  for (int o = 0; o < c->m; ++o)
+    HIP_TRY(hipMemcpyAsync(parity[o], d_par + o * stride, shard_len, hipMemcpyDeviceToHost,
+                           c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return CEC_OK;
+}
+
+// Stages [old bytes of the changed shards][their new bytes][m parity shards].
+int cec_update(cec_codec* c, uint8_t* const* shards, const uint8_t* const* new_data,
+               size_t shard_len) {
+  if (!c || !shards || !new_data) return set_err(CEC_EINVAL, "null");
+  int rc = check_acc_shape(1, shard_len);
+  if (rc) return rc;
+  std::vector<int> ch;
+  for (int j = 0; j < c->k; ++j) {
+    if (!new_data[j]) continue;
+    if (!shards[j]) return set_err(CEC_EINVAL, "new data for a shard whose old bytes are missing");
+    ch.push_back(j);
+  }
+  for (int o = 0; o < c->m; ++o)
+    if (!shards[c->k + o]) return set_err(CEC_EINVAL, "null parity shard");
+  if (ch.empty()) return CEC_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t stride = pad256(shard_len), nc = ch.size();
+  rc = ensure(&c->stage, &c->stage_bytes, stride * (2 * nc + (size_t)c->m), c->stream);
+  if (rc) return rc;
+  uint8_t* d_new = c->stage + nc * stride;
+  uint8_t* d_par = c->stage + 2 * nc * stride;
+  std::vector<uint32_t> slots(nc);
+  std::vector<uint8_t> coef(nc * c->m);
+  for (size_t i = 0; i < nc; ++i) {
+    HIP_TRY(hipMemcpyAsync(c->stage + i * stride, shards[ch[i]], shard_len,
+                           hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_new + i * stride, new_data[ch[i]], shard_len, hipMemcpyHostToDevice,
+                           c->stream));
+    slots[i] = (uint32_t)i;
+    parity_column(c, ch[i], &coef[i * c->m]);
+  }
+  for (int o = 0; o < c->m; ++o)
+    HIP_TRY(hipMemcpyAsync(d_par + o * stride, shards[c->k + o], shard_len,
+                           hipMemcpyHostToDevice, c->stream));
+  cec::launch_acc(c->stage, d_new, 0, stride, d_par, 0, stride, shard_len, slots.data(),
+                  coef.data(), (int)nc, c->m, true, 1, c->stream);
+  rc = check_launch();
+  if (rc) return rc;
+  for (int o = 0; o < c->m; ++o)
+    HIP_TRY(hipMemcpyAsync(shards[c->k + o], d_par + o * stride, shard_len,
+                           hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return CEC_OK;
 }
 

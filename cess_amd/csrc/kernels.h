@@ -192,6 +192,23 @@ void launch_chunk_gather(const Layout& L, int nshards, uint64_t nfrag, const uin
 void launch_xor_reduce(uint8_t* dst, const uint8_t* src, uint32_t nsrc, uint64_t stride,
                        uint64_t len, hipStream_t st);
 
+// Parity accumulation (acc.hip; cec_encode_idx_batch, cec_update_batch): for every segment s and
+// output o < nout
+//   par[o] ^= XOR_{j < nin} coef[j * nout + o] * x_j     (accumulate; else par[o] = ...)
+// with par[o] at parity + s * par_seg_stride + o * par_shard_stride and x_j the len bytes at
+// in_a + s * in_seg_stride + slots[j] * in_slot_stride, XORed with the bytes at the same offset
+// from in_b when in_b is not null (Update: old ^ new). Host arrays `slots` and `coef` are copied
+// into the kernel arguments (launches of at most kRtMaxOut outputs from kAccMaxIn inputs; input
+// chunks after the first accumulate), so the kernels read no other device memory than the shards.
+// 16-byte columns when every base and every stride in use is a 16-byte multiple (a length that is
+// not gets a byte tail), byte-wise for the whole call otherwise.
+constexpr int kAccMaxIn = 8;
+void launch_acc(const uint8_t* in_a, const uint8_t* in_b, uint64_t in_seg_stride,
+                uint64_t in_slot_stride, uint8_t* parity, uint64_t par_seg_stride,
+                uint64_t par_shard_stride, uint64_t len, const uint32_t* slots,
+                const uint8_t* coef, int nin, int nout, bool accumulate, uint64_t nseg,
+                hipStream_t st);
+
 // ok[s] = 0 for every segment s whose seg_bytes of a and b differ (ok preset by the caller).
 void launch_cmp_segments(const uint8_t* a, const uint8_t* b, uint64_t seg_bytes, uint64_t nseg,
                          uint8_t* ok, hipStream_t st);

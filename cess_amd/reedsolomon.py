@@ -1,8 +1,8 @@
 """klauspost/reedsolomon-shaped encoder over libcessec (MI355X).
 
 This mirrors the off-chain codec API whose outputs the CESS chain records:
-`New(k, m)` returns an Encoder with Encode / Verify / Reconstruct / ReconstructData / Split /
-Join, the same argument meaning and the same error names (ErrTooFewShards, ErrShardNoData,
+`New(k, m)` returns an Encoder with Encode / EncodeIdx / Update / Verify / Reconstruct /
+ReconstructData / ReconstructSome / Split / Join, the same argument meaning and the same error names (ErrTooFewShards, ErrShardNoData,
 ErrShardSize, ErrShortData, ErrInvShardNum, ErrMaxShardNum, ErrReconstructRequired). Shards are
 host buffers (numpy uint8 arrays / bytearrays) of equal length; a missing shard is None or empty.
 
@@ -285,6 +285,57 @@ class Encoder:
         for i in want:
             shards[i] = d_shards[i].cpu().numpy()
 
+    def EncodeIdx(self, dataShard, idx: int, parity: Sequence) -> None:
+        """klauspost EncodeIdx: add data shard `idx`'s contribution to the m parity shards in
+        place, parity[o] ^= E[k+o][idx] * dataShard. Feeding every data shard once into zeroed
+        parity, in any order, gives Encode's parity (cec_encode_idx)."""
+        if not 0 <= idx < self.DataShards:
+            raise ErrInvShardNum(ErrInvShardNum.__doc__)
+        if len(parity) != self.ParityShards:
+            raise ErrTooFewShards(ErrTooFewShards.__doc__)
+        if any(p is None for p in parity):
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        if not _present(dataShard):
+            raise ErrShardNoData(ErrShardNoData.__doc__)
+        if self.ParityShards == 0:
+            return
+        size = self._check_shards(parity, nil_ok=False)
+        if len(dataShard) != size:
+            raise ErrShardSize(ErrShardSize.__doc__)
+        src = np.frombuffer(dataShard, np.uint8) if isinstance(dataShard, bytes) \
+            else _as_u8(dataShard)
+        arrs = [_as_u8(p) for p in parity]
+        check(self._lib.cec_encode_idx(self._h, src.ctypes.data, idx, _ptr_array(arrs), size),
+              "EncodeIdx")
+
+    def Update(self, shards: Sequence, newDatashards: Sequence) -> None:
+        """klauspost Update: `shards` is an encoded segment (k + m; an unchanged data shard may
+        be None), `newDatashards` the k data shards with None (or empty) for unchanged ones. The
+        parity shards are brought up to date in place from the old and new bytes of the changed
+        shards only; the data shards are not written (cec_update)."""
+        if len(shards) != self.Shards or len(newDatashards) != self.DataShards:
+            raise ErrTooFewShards(ErrTooFewShards.__doc__)
+        k = self.DataShards
+        size = self._check_shards(list(shards) + list(newDatashards), nil_ok=True)
+        if any(not _present(p) for p in shards[k:]):
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        changed = [j for j in range(k) if _present(newDatashards[j])]
+        if any(not _present(shards[j]) for j in changed):
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        if not changed or self.ParityShards == 0:
+            return
+
+        def ro(b):
+            return np.frombuffer(b, np.uint8) if isinstance(b, bytes) else _as_u8(b)
+
+        old = {j: ro(shards[j]) for j in changed}
+        new = {j: ro(newDatashards[j]) for j in changed}
+        par = [_as_u8(p) for p in shards[k:]]
+        sh = (c_void_p * self.Shards)(*([old[j].ctypes.data if j in old else None
+                                         for j in range(k)] + [p.ctypes.data for p in par]))
+        nd = (c_void_p * k)(*[new[j].ctypes.data if j in new else None for j in range(k)])
+        check(self._lib.cec_update(self._h, sh, nd, size), "Update")
+
     def EncodeDevice(self, shards: Sequence, stream=None) -> None:
         """Encode one segment whose k + m shards are separate 1-D uint8 device tensors: the m
         parity tensors are written (cec_encode_ptrs). Enqueued on `stream` (default: torch's
@@ -390,6 +441,29 @@ class Encoder:
         """Enqueue encode of nseg segments ([nseg][k][len] -> [nseg][m][len]) on `stream`."""
         check(self._lib.cec_encode_batch(self._h, _dev_ptr(d_data), _dev_ptr(d_parity), nseg,
                                            shard_len, _stream_handle(stream)), "EncodeBatch")
+
+    def EncodeIdxBatch(self, d_shard, shard_seg_stride: int, idx: int, d_parity, nseg: int,
+                       shard_len: int, accumulate: bool = True, stream=None) -> None:
+        """EncodeIdx over an HBM batch (cec_encode_idx_batch): data shard `idx` of segment s is at
+        d_shard + s * shard_seg_stride; d_parity is [nseg][m][len]. accumulate=False overwrites
+        the parity without reading it (the first shard of a segment needs no zeroing pass)."""
+        if not 0 <= idx < self.DataShards:
+            raise ErrInvShardNum(ErrInvShardNum.__doc__)
+        check(self._lib.cec_encode_idx_batch(
+            self._h, _dev_ptr(d_shard), shard_seg_stride, idx, _dev_ptr(d_parity), nseg,
+            shard_len, 1 if accumulate else 0, _stream_handle(stream)), "EncodeIdxBatch")
+
+    def UpdateBatch(self, d_old, d_new, d_parity, nseg: int, shard_len: int, changed,
+                    stream=None) -> None:
+        """Update over an HBM batch (cec_update_batch): d_old and d_new are [nseg][k][len], of
+        which only the slots flagged in `changed` (k flags, one set for the whole call) are read;
+        d_parity ([nseg][m][len]) is brought up to date in place."""
+        ch = np.ascontiguousarray(np.asarray(changed, dtype=np.uint8))
+        if ch.shape != (self.DataShards,):
+            raise ErrTooFewShards(ErrTooFewShards.__doc__)
+        check(self._lib.cec_update_batch(
+            self._h, _dev_ptr(d_old), _dev_ptr(d_new), _dev_ptr(d_parity), nseg, shard_len,
+            ch.ctypes.data_as(POINTER(c_uint8)), _stream_handle(stream)), "UpdateBatch")
 
     def ReconstructBatch(self, d_data, d_parity, nseg: int, shard_len: int, present,
                          data_only: bool = False, stream=None) -> None:

@@ -15,8 +15,8 @@
  *   and the restoral (repair) flow whose off-chain step is a single-fragment reconstruct
  *     generate_restoral_order / restoral_order_complete   c-pallets/file-bank/src/lib.rs:943-1122
  *   The entry points below mirror the off-chain codec API those records come from
- *   (klauspost/reedsolomon Encoder: New / Encode / Reconstruct / ReconstructData / Verify /
- *   Split — not vendored in the reference), one function per operation,
+ *   (klauspost/reedsolomon Encoder: New / Encode / EncodeIdx / Update / Reconstruct /
+ *   ReconstructData / ReconstructSome / Verify / Split — not vendored in the reference), one function per operation,
  *   plus batched device-resident forms for HBM-resident segment batches.
  *
  * Conventions: GF(2^8), polynomial 0x11D, systematic Vandermonde matrix.
@@ -171,6 +171,53 @@ int cec_verify_batch(cec_codec* codec, const uint8_t* d_data, const uint8_t* d_p
  * device holding the buffers (no codec: the caller's current device and stream decide). */
 int cec_xor_batch(uint8_t* d_dst, const uint8_t* d_src, size_t nsrc, size_t src_stride,
                   size_t len, void* hip_stream);
+/* ---- parity accumulated shard by shard (klauspost EncodeIdx and Update) -----------------------
+ * Both are one primitive on the codec's encode matrix E (cec_matrix; row k+o is parity shard o):
+ *   parity[o] ^= E[k+o][j] * x_j   for every o < m,
+ * with x_j a data shard (EncodeIdx) or old_j ^ new_j of a changed data shard (Update).
+ *  - EncodeIdx: feeding every data shard exactly once into zeroed parity, in any order, gives
+ *    cec_encode_batch's parity; a subset gives the encode of the segment with the other data
+ *    shards zero. No data shard is written.
+ *  - Update: parity[o] ^= XOR over the changed shards j of E[k+o][j] * (old_j ^ new_j). Only the
+ *    parity is written; the old data keeps its bytes and the caller swaps in the new ones.
+ *  - Reads: the named shard (EncodeIdx) or the old and new bytes of the flagged slots (Update), and
+ *    the parity (not read with accumulate == 0). Nothing else of the batch is touched.
+ *  - Writes: the nseg * m * shard_len parity bytes, nothing else.
+ *  - Validation happens before anything is enqueued; on any error no byte is written. CEC_EINVAL:
+ *    codec or a needed pointer NULL, idx outside [0, k), nseg > 1 with shard_seg_stride <
+ *    shard_len, or bytes the call reads overlapping the parity range it writes. CEC_ESHARDLEN:
+ *    shard_len == 0. nseg == 0, or no flag set, is a no-op that returns CEC_OK.
+ *  - Alignment: any alignment and any shard_len >= 1 is correct. When every base and stride is a
+ *    16-byte multiple the kernels take 16-byte columns (a shard_len that is not gets a byte tail);
+ *    otherwise the whole call runs byte-wise.
+ *  - The batch calls enqueue on hip_stream and do not wait. Their coefficients travel in the
+ *    kernel arguments: these calls read no codec-owned device memory, so there is no program to
+ *    cache or to retire. They are not exercised under HIP graph capture in the tests. */
+/* EncodeIdx on device buffers. Shard idx of segment s is at d_shard + s*shard_seg_stride
+ * (stride k*shard_len for a batch in the library's layout with d_shard = d_data + idx*shard_len,
+ * shard_len for shards packed alone). d_parity: [nseg][m][shard_len].
+ * accumulate != 0: parity ^= E*x (klauspost). accumulate == 0: parity = E*x, the old parity not
+ * read: the first shard of a segment then needs no zeroing pass. */
+int cec_encode_idx_batch(cec_codec* codec, const uint8_t* d_shard, size_t shard_seg_stride, int idx,
+                         uint8_t* d_parity, size_t nseg, size_t shard_len, int accumulate,
+                         void* hip_stream);
+/* Update on device buffers. d_old, d_new: [nseg][k][shard_len]. changed: HOST array of k flags,
+ * one set for the whole call. Only flagged slots of d_old and d_new are read. d_parity
+ * ([nseg][m][shard_len]) is updated in place. */
+int cec_update_batch(cec_codec* codec, const uint8_t* d_old, const uint8_t* d_new, uint8_t* d_parity,
+                     size_t nseg, size_t shard_len, const uint8_t* changed, void* hip_stream);
+/* Host-buffer forms (klauspost-shaped, staged through HBM, synchronous). Only what is read is
+ * staged: the shard and the m parity shards, or the old and new bytes of the changed shards and the
+ * parity; the parity is copied back.
+ * cec_encode_idx: parity holds m host pointers (none NULL); accumulates.
+ * cec_update: shards holds k+m pointers, a NULL data entry = unchanged; new_data holds k, NULL =
+ * unchanged. CEC_EINVAL where new_data[j] is set and shards[j] is NULL, or a parity pointer is
+ * NULL. Nothing changed: CEC_OK, nothing done. */
+int cec_encode_idx(cec_codec* codec, const uint8_t* data_shard, int idx, uint8_t* const* parity,
+                   size_t shard_len);
+int cec_update(cec_codec* codec, uint8_t* const* shards, const uint8_t* const* new_data,
+               size_t shard_len);
+
 /* SHA-256 of every shard of every segment in the batch layout, as 64 lowercase hex chars:
  * d_hex[(seg*(k+m) + shard)*64 ...]. d_parity may be NULL to hash the k data shards only, in
  * which case the index is seg*k + shard. */

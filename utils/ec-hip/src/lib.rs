@@ -175,6 +175,17 @@ pub mod sys {
                                 stream: *mut c_void) -> c_int;
         pub fn cec_xor_batch(d_dst: *mut u8, d_src: *const u8, nsrc: usize, src_stride: usize,
                              len: usize, stream: *mut c_void) -> c_int;
+        pub fn cec_encode_idx_batch(c: *mut cec_codec, d_shard: *const u8,
+                                    shard_seg_stride: usize, idx: c_int, d_parity: *mut u8,
+                                    nseg: usize, shard_len: usize, accumulate: c_int,
+                                    stream: *mut c_void) -> c_int;
+        pub fn cec_update_batch(c: *mut cec_codec, d_old: *const u8, d_new: *const u8,
+                                d_parity: *mut u8, nseg: usize, shard_len: usize,
+                                changed: *const u8, stream: *mut c_void) -> c_int;
+        pub fn cec_encode_idx(c: *mut cec_codec, data_shard: *const u8, idx: c_int,
+                              parity: *const *mut u8, shard_len: usize) -> c_int;
+        pub fn cec_update(c: *mut cec_codec, shards: *const *mut u8,
+                          new_data: *const *const u8, shard_len: usize) -> c_int;
         pub fn cec_sha256_batch(c: *mut cec_codec, d_data: *const u8, d_parity: *const u8,
                                 nseg: usize, shard_len: usize, d_hex: *mut u8,
                                 stream: *mut c_void) -> c_int;
@@ -457,6 +468,61 @@ impl ReedSolomon {
     /// Recreate only the missing data shards.
     pub fn reconstruct_data(&self, shards: &mut [Option<Vec<u8>>]) -> Result<(), Error> {
         self.reconstruct_inner(shards, true)
+    }
+
+    /// `reed-solomon-erasure` `encode_single`: add data shard `i_data`'s contribution to the
+    /// parity shards `shards[k..]` in place (`cec_encode_idx`: parity[o] ^= E[k+o][i] * shard).
+    /// Feeding every data shard once into zeroed parity, in any order, gives `encode`'s parity.
+    pub fn encode_single(&self, i_data: usize, shards: &mut [&mut [u8]]) -> Result<(), Error> {
+        if shards.len() != self.k + self.m || i_data >= self.k {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        let (p, len) = Self::ptrs(shards)?;
+        check(unsafe {
+            sys::cec_encode_idx(self.c, p[i_data] as *const u8, i_data as c_int,
+                                p[self.k..].as_ptr(), len)
+        })
+    }
+
+    /// `encode_single_sep`: the same with the data shard and the m parity shards held apart.
+    pub fn encode_single_sep(&self, i_data: usize, single_data: &[u8],
+                             parity: &mut [&mut [u8]]) -> Result<(), Error> {
+        if parity.len() != self.m || i_data >= self.k {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        let (p, len) = Self::ptrs(parity)?;
+        if single_data.len() != len {
+            return Err(Error::from_code(CEC_ESHARDLEN));
+        }
+        check(unsafe {
+            sys::cec_encode_idx(self.c, single_data.as_ptr(), i_data as c_int, p.as_ptr(), len)
+        })
+    }
+
+    /// klauspost `Update` (`cec_update`): `shards` is an encoded segment (k + m, `None` for a data
+    /// shard that did not change), `new_data` the k data shards with `None` for unchanged ones.
+    /// The parity shards are brought up to date in place from the old and new bytes of the changed
+    /// shards only; the old data shards keep their bytes.
+    pub fn update(&self, shards: &mut [Option<Vec<u8>>], new_data: &[Option<&[u8]>])
+                  -> Result<(), Error> {
+        if shards.len() != self.k + self.m || new_data.len() != self.k {
+            return Err(Error::from_code(CEC_ETOOFEW));
+        }
+        let len = shards[self.k..].iter().flatten().map(|s| s.len()).next()
+            .ok_or(Error::from_code(CEC_EINVAL))?;
+        if shards.iter().flatten().any(|s| s.len() != len)
+            || new_data.iter().flatten().any(|s| s.len() != len) {
+            return Err(Error::from_code(CEC_ESHARDLEN));
+        }
+        let p: Vec<*mut u8> = shards
+            .iter_mut()
+            .map(|s| match s { Some(v) => v.as_mut_ptr(), None => std::ptr::null_mut() })
+            .collect();
+        let n: Vec<*const u8> = new_data
+            .iter()
+            .map(|s| match s { Some(v) => v.as_ptr(), None => std::ptr::null() })
+            .collect();
+        check(unsafe { sys::cec_update(self.c, p.as_ptr(), n.as_ptr(), len) })
     }
 
     /// Scattered device shards (`cec_reconstruct_ptrs`): `src` and `dst` hold `nseg * (k + m)`
