@@ -541,7 +541,7 @@ void launch_chunk(const KernelOpts& o, const Layout& L, const uint32_t* chunk,
   // vs k_rthx: one lost fragment 5.84 vs 4.03 TB/s, two 4.89 vs 3.75, three 3.89 vs 3.55, four
   // 3.36 vs 3.33; RS(10,4) encode 3.54 vs 3.41; bench.py --config 6 --erasures e / --config 8,
   // profiles/r02/rtb_sweep.txt)
-  if ((o.rt_mode == 3 || (o.rt_mode == 0 && nob <= 4 && nin >= 4)) &&
+  if (cec::rt_takes_rtb(o, nob, nin) &&
       cec::launch_matvec_rtb(L, chunk, per_seg, nob, seg_list, nseg, st, o.ct_variant))
     return;
   if (nin <= cec::kRthMaxIn &&
@@ -632,16 +632,43 @@ std::string some_key(const uint8_t* present, const uint8_t* required, int k, int
   return key;
 }
 
-// Decode program for one erasure pattern (LRU-cached). Nothing is evicted here: the caller
-// evicts after its launches are enqueued and marked (evict_decode), so a program resolved
-// earlier in the same call is never dropped under it. With `required`, only the lost shards it
-// flags are outputs (rows of the same decode: the survivors read do not change).
+// The decode LRU. cache_find makes a hit the most recently used entry; nothing is evicted by
+// cache_put: the caller evicts after its launches are enqueued and marked (evict_decode), so a
+// program resolved earlier in the same call is never dropped under it.
+ProgPtr cache_find(cec_codec* c, const std::string& key) {
+  auto it = c->decode_cache.find(key);
+  if (it == c->decode_cache.end()) return nullptr;
+  c->lru.splice(c->lru.begin(), c->lru, it->second.lru);
+  return it->second.prog;
+}
+
+void cache_put(cec_codec* c, std::string key, const ProgPtr& prog) {
+  c->lru.push_front(key);
+  c->decode_cache.emplace(std::move(key), cec_codec::Entry{prog, c->lru.begin()});
+}
+
+// Solve the erasure pattern `flags` (n flags of 0 / 1) of the code with encode matrix E into
+// sc.plan: the rows that rebuild every lost shard from survivor_set's survivors (cec_survivors).
+int solve_pattern(int k, int m, const BigMat& E, const uint8_t* flags, bool data_only,
+                  cec_codec::PlanScratch& sc) {
+  uint8_t rd[cec::kMaxShards];
+  if (!cec::survivor_set(k, m, flags, rd) ||
+      cec::gf_decode_plan_sys(k, m, flags, data_only, E, sc.plan, sc.a, sc.ainv, sc.work, rd) != 0)
+    return set_err(CEC_ETOOFEW, "fewer than k shards present");
+  return CEC_OK;
+}
+
+// Decode program for one erasure pattern (LRU-cached). With `required`, only the lost shards it
+// flags are outputs (rows of the same decode: the survivors read do not change). `key_out`
+// receives the pattern's cache key.
 int get_decode(cec_codec* c, const uint8_t* present, bool data_only, ProgPtr* out,
-               HostImages* keep = nullptr, const uint8_t* required = nullptr) {
+               HostImages* keep = nullptr, const uint8_t* required = nullptr,
+               std::string* key_out = nullptr) {
   const int n = c->k + c->m;
   uint8_t want[cec::kMaxShards];
   std::string key = required ? some_key(present, required, c->k, n, data_only, want)
                              : pattern_key(present, n, data_only);
+  if (key_out) *key_out = key;
   const bool some = key[0] == 'R';
   if (some && !std::memchr(want, 1, n)) {
     // nothing asked for: nothing to do, whatever is present (klauspost returns before it counts
@@ -649,20 +676,13 @@ int get_decode(cec_codec* c, const uint8_t* present, bool data_only, ProgPtr* ou
     *out = std::make_shared<const Program>();
     return CEC_OK;
   }
-  auto it = c->decode_cache.find(key);
-  if (it != c->decode_cache.end()) {
-    c->lru.splice(c->lru.begin(), c->lru, it->second.lru);
-    *out = it->second.prog;
-    return CEC_OK;
-  }
+  if ((*out = cache_find(c, key))) return CEC_OK;
   auto& sc = c->plan_scratch();
   auto* plan = &sc.plan;
-  uint8_t flags[cec::kMaxShards], rd[cec::kMaxShards];
-  for (int i = 0; i < n; ++i) flags[i] = key[1 + i];
-  if (!cec::survivor_set(c->k, c->m, flags, rd) ||
-      cec::gf_decode_plan_sys(c->k, c->m, flags, data_only, *c->E, *plan, sc.a, sc.ainv, sc.work,
-                              rd) != 0)
-    return set_err(CEC_ETOOFEW, "fewer than k shards present");
+  uint8_t flags[cec::kMaxShards];
+  std::memcpy(flags, key.data() + 1, n);
+  int rc = solve_pattern(c->k, c->m, *c->E, flags, data_only, sc);
+  if (rc) return rc;
   if (some) {  // keep the wanted rows
     int w = 0;
     for (int o = 0; o < plan->nout; ++o) {
@@ -690,15 +710,14 @@ int get_decode(cec_codec* c, const uint8_t* present, bool data_only, ProgPtr* ou
     const uint8_t* wf = some ? want : nullptr;  // the plans' output lists shrink to the subset
     const bool fd = wide && cec::fftdec_plan_m(read, flags, data_only, &fdp, wf);
     const bool fdd = wide && cec::fftdec_plan_d(read, flags, data_only, &fddp, wf);
-    int rc = build_program(c->pool, c->stream, plan->in_idx, c->k, plan->out_idx, plan->nout,
-                           plan->coef, &prog, false, keep, fd ? &fdp : nullptr,
-                           fdd ? &fddp : nullptr);
+    rc = build_program(c->pool, c->stream, plan->in_idx, c->k, plan->out_idx, plan->nout,
+                       plan->coef, &prog, false, keep, fd ? &fdp : nullptr,
+                       fdd ? &fddp : nullptr);
     if (rc) return rc;
   } else {
     prog = std::make_shared<const Program>();
   }
-  c->lru.push_front(key);
-  c->decode_cache.emplace(std::move(key), cec_codec::Entry{prog, c->lru.begin()});
+  cache_put(c, std::move(key), prog);
   *out = std::move(prog);
   return CEC_OK;
 }
@@ -708,25 +727,19 @@ int get_decode(cec_codec* c, const uint8_t* present, bool data_only, ProgPtr* ou
 // in `held`. The rebuild is linear in the survivors, so the XOR of the partials over any
 // partition of the survivors is the full rebuild. No held survivor: a zero program (one input
 // column with zero coefficients), so the outputs are still written (as zeros). Cached in the
-// decode LRU under its own key.
+// decode LRU under its own key, which `key_out` receives.
 int get_partial(cec_codec* c, const uint8_t* present, const uint8_t* held, bool data_only,
-                ProgPtr* out, HostImages* keep = nullptr) {
+                ProgPtr* out, HostImages* keep = nullptr, std::string* key_out = nullptr) {
   const int n = c->k + c->m;
   std::string key = partial_key(present, held, n, data_only);
-  auto it = c->decode_cache.find(key);
-  if (it != c->decode_cache.end()) {
-    c->lru.splice(c->lru.begin(), c->lru, it->second.lru);
-    *out = it->second.prog;
-    return CEC_OK;
-  }
+  if (key_out) *key_out = key;
+  if ((*out = cache_find(c, key))) return CEC_OK;
   auto& sc = c->plan_scratch();
   auto* plan = &sc.plan;
-  uint8_t flags[cec::kMaxShards], rd[cec::kMaxShards];
-  for (int i = 0; i < n; ++i) flags[i] = present[i] ? 1 : 0;
-  if (!cec::survivor_set(c->k, c->m, flags, rd) ||
-      cec::gf_decode_plan_sys(c->k, c->m, flags, data_only, *c->E, *plan, sc.a, sc.ainv, sc.work,
-                              rd) != 0)
-    return set_err(CEC_ETOOFEW, "fewer than k shards present");
+  uint8_t flags[cec::kMaxShards];
+  std::memcpy(flags, key.data() + 1, n);
+  int rc = solve_pattern(c->k, c->m, *c->E, flags, data_only, sc);
+  if (rc) return rc;
   ProgPtr prog;
   if (plan->nout > 0) {
     uint8_t in_sub[cec::kMaxShards];
@@ -742,14 +755,13 @@ int get_partial(cec_codec* c, const uint8_t* present, const uint8_t* held, bool 
       in_sub[0] = plan->in_idx[0];
       nsub = 1;
     }
-    int rc = build_program(c->pool, c->stream, in_sub, nsub, plan->out_idx, plan->nout, *coef,
-                           &prog, true, keep);
+    rc = build_program(c->pool, c->stream, in_sub, nsub, plan->out_idx, plan->nout, *coef, &prog,
+                       true, keep);
     if (rc) return rc;
   } else {
     prog = std::make_shared<const Program>();
   }
-  c->lru.push_front(key);
-  c->decode_cache.emplace(std::move(key), cec_codec::Entry{prog, c->lru.begin()});
+  cache_put(c, std::move(key), prog);
   *out = std::move(prog);
   return CEC_OK;
 }
@@ -873,16 +885,48 @@ Layout stage_layout(cec_codec* c, size_t len) {
   return L;
 }
 
-// Build the plan of a per-segment reconstruct for the pattern array `pkey` (nseg * n flags +
-// data_only + force_generic) into *out; device arrays are uploaded and complete on return.
-// partial: pkey holds 2n flags per segment (present, then held) and the programs are partial
-// (cec_reconstruct_partial_batch). some: pkey holds 2n flags per segment (present, then required)
-// and the programs write the required lost shards only (cec_reconstruct_some_batch).
-int build_ps_plan(cec_codec* c, const std::string& pkey, size_t nseg, bool data_only,
-                  std::unique_ptr<PsPlan>* out, bool partial = false, bool fdok = false,
-                  size_t shard_len = 0, bool some = false) {
+// The host-buffer calls: room for `nshards` staged shards of `len` bytes, and the copies of the
+// `count` shards host[0..count) up to consecutive stage slots from `dev`, or down from them, on
+// the codec's stream (the caller synchronises once, at the end).
+int stage_ensure(cec_codec* c, size_t nshards, size_t len) {
+  return ensure(&c->stage, &c->stage_bytes, pad256(len) * nshards, c->stream);
+}
+int stage_up(cec_codec* c, uint8_t* dev, const uint8_t* const* host, int count, size_t len) {
+  for (int i = 0; i < count; ++i)
+    HIP_TRY(hipMemcpyAsync(dev + i * pad256(len), host[i], len, hipMemcpyHostToDevice, c->stream));
+  return CEC_OK;
+}
+int stage_down(cec_codec* c, uint8_t* const* host, const uint8_t* dev, int count, size_t len) {
+  for (int i = 0; i < count; ++i)
+    HIP_TRY(hipMemcpyAsync(host[i], dev + i * pad256(len), len, hipMemcpyDeviceToHost, c->stream));
+  return CEC_OK;
+}
+
+// New patterns' program uploads stay in flight until one synchronisation per call (not per
+// pattern: 64 new RS(32,32) patterns cost ~1 ms of waits otherwise); every return path waits for
+// them before their host images go.
+struct Uploads {
+  hipStream_t st;
+  PinnedArena& arena;
+  ~Uploads() {
+    if (arena.busy()) (void)hipStreamSynchronize(st);
+    arena.reset();
+  }
+};
+
+// What a per-segment plan rebuilds, and so what its pattern array `pkey` holds per segment: kFull
+// n presence flags (cec_reconstruct_batch); kPartial n presence then n held flags, the programs
+// partial (cec_reconstruct_partial_batch); kSome n presence then n required flags, the programs
+// writing the required lost shards only (cec_reconstruct_some_batch).
+enum PsKind { kFull, kPartial, kSome };
+
+// Build the plan of a per-segment reconstruct for the pattern array `pkey` (a kind tag, the flags
+// of nseg segments, then the options the plan depends on) into *out; device arrays are uploaded
+// and complete on return. fdok: the layout fits the FFT-domain decoders (never for kPartial).
+int build_ps_plan(cec_codec* c, const std::string& pkey, size_t nseg, PsKind kind, bool data_only,
+                  bool fdok, size_t shard_len, std::unique_ptr<PsPlan>* out) {
   const int n = c->k + c->m;
-  const int per = partial || some ? 2 * n : n;
+  const int per = kind == kFull ? n : 2 * n;
   auto plan = std::make_unique<PsPlan>();
   plan->key = pkey;
   // group segments by pattern, in first-appearance order (deterministic launch order)
@@ -899,27 +943,17 @@ int build_ps_plan(cec_codec* c, const std::string& pkey, size_t nseg, bool data_
   }
   bool all_ct = !c->force_generic;
   std::vector<std::pair<ProgPtr, const std::vector<uint32_t>*>> progs, reencode, fdg[5];
-  // new patterns' program uploads stay in flight until the one synchronisation below (one per
-  // plan, not per pattern: 64 new RS(32,32) patterns cost ~1 ms of waits otherwise); every return
-  // path waits for them before their host images go
-  struct Uploads {
-    hipStream_t st;
-    PinnedArena& arena;
-    ~Uploads() {
-      if (arena.busy()) (void)hipStreamSynchronize(st);
-      arena.reset();
-    }
-  } up{c->stream, c->arena};
+  Uploads up{c->stream, c->arena};  // synchronised once, below
   for (auto& g : groups) {
     ProgPtr p;
+    std::string key;
     const uint8_t* flags = reinterpret_cast<const uint8_t*>(g.first.data());
-    int rc = partial ? get_partial(c, flags, flags + n, data_only, &p, &up.arena)
-                     : get_decode(c, flags, data_only, &p, &up.arena, some ? flags + n : nullptr);
+    int rc = kind == kPartial
+                 ? get_partial(c, flags, flags + n, data_only, &p, &up.arena, &key)
+                 : get_decode(c, flags, data_only, &p, &up.arena,
+                              kind == kSome ? flags + n : nullptr, &key);
     if (rc) return rc;
-    uint8_t want[cec::kMaxShards];
-    plan->keys.push_back(partial ? partial_key(flags, flags + n, n, data_only)
-                         : some  ? some_key(flags, flags + n, c->k, n, data_only, want)
-                                 : pattern_key(flags, n, data_only));
+    plan->keys.push_back(std::move(key));
     if (!p->nout) continue;
     plan->progs.push_back(p);
     if (!c->force_generic && p->single < 0 && is_reencode(c, *p)) {
@@ -1093,6 +1127,33 @@ int launch_ps_plan(cec_codec* c, const PsPlan& p, const Layout& L, hipStream_t s
   return CEC_OK;
 }
 
+// A per-segment reconstruct: the codec's cached plan when `pkey` repeats (degraded-read and repair
+// loops pass the same map each call), else a new one; then its launches and their mark.
+int run_ps_plan(cec_codec* c, const std::string& pkey, size_t nseg, PsKind kind, bool data_only,
+                bool fdok, size_t shard_len, const Layout& L, hipStream_t st) {
+  if (!c->ps || c->ps->key != pkey) {
+    std::unique_ptr<PsPlan> plan;
+    int rc = build_ps_plan(c, pkey, nseg, kind, data_only, fdok, shard_len, &plan);
+    if (rc) return rc;
+    c->drop_plan();  // the old plan's arrays are retired: launches already enqueued keep them
+    c->ps = std::move(plan);
+  } else {
+    for (const auto& key : c->ps->keys) (void)cache_find(c, key);  // they stay recently used
+  }
+  const int rc = launch_ps_plan(c, *c->ps, L, st);
+  // completion point of these launches; only then may evicted programs be retired
+  const int mrc = c->pool.mark(st);
+  evict_decode(c);
+  return rc ? rc : mrc;
+}
+
+// The opening checks of the batched calls, after their null tests.
+int check_batch(size_t nseg, size_t shard_len) {
+  if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
+  if (nseg > 0xffffffffull) return set_err(CEC_EINVAL, "too many segments");
+  return CEC_OK;
+}
+
 }  // namespace
 
 namespace cec {
@@ -1246,8 +1307,7 @@ int cec_get_stat(const cec_codec* c, int stat, uint64_t* value) {
 int cec_encode_batch(cec_codec* c, const uint8_t* d_data, uint8_t* d_parity, size_t nseg,
                      size_t shard_len, void* hip_stream) {
   if (!c || (nseg && (!d_data || !d_parity))) return set_err(CEC_EINVAL, "null");
-  if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
-  if (nseg > 0xffffffffull) return set_err(CEC_EINVAL, "too many segments");
+  if (int rc = check_batch(nseg, shard_len)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   Layout L = batch_layout(c, d_data, d_parity, shard_len);
   return do_encode(c, L, nullptr, (uint32_t)nseg, pick_stream(c, hip_stream));
@@ -1260,22 +1320,15 @@ static int reconstruct_batch_impl(cec_codec* c, uint8_t* d_data, uint8_t* d_pari
                                   const uint8_t* required, int per_segment, int data_only,
                                   void* hip_stream) {
   if (!c || !present || (nseg && (!d_data || !d_parity))) return set_err(CEC_EINVAL, "null");
-  if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
-  if (nseg > 0xffffffffull) return set_err(CEC_EINVAL, "too many segments");
+  int rc = check_batch(nseg, shard_len);
+  if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, hip_stream);
   const int n = c->k + c->m;
   Layout L = batch_layout(c, d_data, d_parity, shard_len);
-  int rc = CEC_OK;
-  if (!per_segment) {
-    ProgPtr p;
-    rc = get_decode(c, present, data_only != 0, &p, nullptr, required);
-    if (rc) return rc;
-    rc = do_decode(c, *p, L, nullptr, (uint32_t)nseg, st);
-  } else {
+  if (per_segment) {
     // Per-segment patterns. Segments are grouped by pattern once and the plan is cached for a
-    // repeated pattern array (degraded-read bench and repair loops pass the same map each
-    // call):
+    // repeated pattern array:
     //  * every pattern has a compile-time single-erasure kernel (RS(2,1)): one mixed-pattern
     //    launch (or one launch per pattern over its segment list);
     //  * otherwise: one multi-pattern run-time launch per (chunk index, bucket), each segment's
@@ -1298,21 +1351,13 @@ static int reconstruct_batch_impl(cec_codec* c, uint8_t* d_data, uint8_t* d_pari
     pkey.push_back((char)c->fftdec_min);
     pkey.push_back((char)c->fftdec_mode);
     for (int b = 0; b < 8; ++b) pkey.push_back((char)(shard_len >> (8 * b)));  // the split rule
-    if (!c->ps || c->ps->key != pkey) {
-      std::unique_ptr<PsPlan> plan;
-      rc = build_ps_plan(c, pkey, nseg, data_only != 0, &plan, false, fdok, shard_len,
-                         required != nullptr);
-      if (rc) return rc;
-      c->drop_plan();  // the old plan's arrays are retired: launches already enqueued keep them
-      c->ps = std::move(plan);
-    } else {
-      for (const auto& key : c->ps->keys) {  // the reused plan's patterns stay recently used
-        auto it = c->decode_cache.find(key);
-        if (it != c->decode_cache.end()) c->lru.splice(c->lru.begin(), c->lru, it->second.lru);
-      }
-    }
-    rc = launch_ps_plan(c, *c->ps, L, st);
+    return run_ps_plan(c, pkey, nseg, required ? kSome : kFull, data_only != 0, fdok, shard_len, L,
+                       st);
   }
+  ProgPtr p;
+  rc = get_decode(c, present, data_only != 0, &p, nullptr, required);
+  if (rc) return rc;
+  rc = do_decode(c, *p, L, nullptr, (uint32_t)nseg, st);
   // completion point of these launches; only then may evicted programs be retired
   int mrc = c->pool.mark(st);
   evict_decode(c);
@@ -1341,17 +1386,13 @@ int cec_decode_rows(int k, int m, const uint8_t* present, const uint8_t* require
     return set_err(CEC_EINVAL, "need k >= 1, m >= 1, k + m <= 256");
   const int n = k + m;
   auto E = std::make_unique<BigMat>();
-  auto a = std::make_unique<BigMat>();
-  auto ainv = std::make_unique<BigMat>();
-  auto work = std::make_unique<WorkMat>();
-  auto plan = std::make_unique<BigPlan>();
-  if (!cec::gf_encode_matrix(k, m, *E, *a, *ainv, *work))
+  auto sc = std::make_unique<cec_codec::PlanScratch>();
+  const BigPlan* plan = &sc->plan;
+  if (!cec::gf_encode_matrix(k, m, *E, sc->a, sc->ainv, sc->work))
     return set_err(CEC_EINVAL, "singular Vandermonde top block");
-  uint8_t flags[cec::kMaxShards], rd[cec::kMaxShards];
+  uint8_t flags[cec::kMaxShards];
   for (int i = 0; i < n; ++i) flags[i] = present[i] ? 1 : 0;
-  if (!cec::survivor_set(k, m, flags, rd) ||
-      cec::gf_decode_plan_sys(k, m, flags, false, *E, *plan, *a, *ainv, *work, rd) != 0)
-    return set_err(CEC_ETOOFEW, "fewer than k shards present");
+  if (int rc = solve_pattern(k, m, *E, flags, false, *sc)) return rc;
   int w = 0;
   for (int o = 0; o < plan->nout; ++o) {  // out_idx ascending, survivors in cec_survivors order
     if (!required[plan->out_idx[o]]) continue;
@@ -1376,14 +1417,7 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
   };
   std::unordered_map<std::string, size_t> gidx;
   std::vector<Group> groups;
-  struct Uploads {  // new patterns' images stay in flight until the one synchronisation below
-    hipStream_t st;
-    PinnedArena& arena;
-    ~Uploads() {
-      if (arena.busy()) (void)hipStreamSynchronize(st);
-      arena.reset();
-    }
-  } up{c->stream, c->arena};
+  Uploads up{c->stream, c->arena};  // synchronised once, with the table's upload
   std::string key(2 * (size_t)n, '\0');
   uintptr_t bits = 0;  // OR of every address read or written: the alignment of the call
   for (size_t s = 0; s < nseg; ++s) {
@@ -1447,9 +1481,7 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
     }
     int o0 = 0;
     for (const RtChunk& ch : p.chunks) {
-      // the cases k_rtb takes in the batch layout (launch_chunk): up to four outputs from four
-      // or more inputs
-      const bool rtb = c->opts.rt_mode == 3 || (c->opts.rt_mode == 0 && ch.nob <= 4 && ch.nin >= 4);
+      const bool rtb = cec::rt_takes_rtb(c->opts, ch.nob, ch.nin);  // as launch_chunk
       Launch& l = launch_of(rtb && ch.nob <= 4 ? 1 : 2, ch.nob, (uint32_t)(1 + ch.nin + ch.nob));
       for (uint32_t s : g.segs) {
         const size_t r0 = l.rows.size();
@@ -1503,8 +1535,7 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
 int cec_reconstruct_ptrs(cec_codec* c, const uint8_t* const* src, uint8_t* const* dst,
                          size_t nseg, size_t shard_len, void* hip_stream) {
   if (!c || (nseg && (!src || !dst))) return set_err(CEC_EINVAL, "null");
-  if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
-  if (nseg > 0xffffffffull) return set_err(CEC_EINVAL, "too many segments");
+  if (int rc = check_batch(nseg, shard_len)) return rc;
   if (nseg == 0) return CEC_OK;
   HIP_TRY(hipSetDevice(c->device));
   return reconstruct_ptrs_impl(c, src, dst, nseg, shard_len, pick_stream(c, hip_stream));
@@ -1513,8 +1544,7 @@ int cec_reconstruct_ptrs(cec_codec* c, const uint8_t* const* src, uint8_t* const
 int cec_encode_ptrs(cec_codec* c, const uint8_t* const* d_data_ptrs, uint8_t* const* d_parity_ptrs,
                     size_t nseg, size_t shard_len, void* hip_stream) {
   if (!c || (nseg && (!d_data_ptrs || !d_parity_ptrs))) return set_err(CEC_EINVAL, "null");
-  if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
-  if (nseg > 0xffffffffull) return set_err(CEC_EINVAL, "too many segments");
+  if (int rc = check_batch(nseg, shard_len)) return rc;
   if (nseg == 0) return CEC_OK;
   const int n = c->k + c->m;
   std::vector<const uint8_t*> src(nseg * n, nullptr);
@@ -1536,8 +1566,7 @@ int cec_reconstruct_partial_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_pari
                                   int data_only, void* hip_stream) {
   if (!c || !present || !held || (nseg && (!d_data || !d_parity)))
     return set_err(CEC_EINVAL, "null");
-  if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
-  if (nseg > 0xffffffffull) return set_err(CEC_EINVAL, "too many segments");
+  if (int rc = check_batch(nseg, shard_len)) return rc;
   if (nseg == 0) return CEC_OK;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, hip_stream);
@@ -1553,30 +1582,13 @@ int cec_reconstruct_partial_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_pari
   }
   pkey.push_back(data_only ? 1 : 0);
   pkey.push_back(c->force_generic ? 1 : 0);
-  int rc = CEC_OK;
-  if (!c->ps || c->ps->key != pkey) {
-    std::unique_ptr<PsPlan> plan;
-    rc = build_ps_plan(c, pkey, nseg, data_only != 0, &plan, true);
-    if (rc) return rc;
-    c->drop_plan();
-    c->ps = std::move(plan);
-  } else {
-    for (const auto& key : c->ps->keys) {
-      auto it = c->decode_cache.find(key);
-      if (it != c->decode_cache.end()) c->lru.splice(c->lru.begin(), c->lru, it->second.lru);
-    }
-  }
-  rc = launch_ps_plan(c, *c->ps, L, st);
-  int mrc = c->pool.mark(st);
-  evict_decode(c);
-  return rc ? rc : mrc;
+  return run_ps_plan(c, pkey, nseg, kPartial, data_only != 0, false, 0, L, st);
 }
 
 int cec_verify_batch(cec_codec* c, const uint8_t* d_data, const uint8_t* d_parity, size_t nseg,
                      size_t shard_len, uint8_t* d_ok, void* hip_stream) {
   if (!c || !d_ok || (nseg && (!d_data || !d_parity))) return set_err(CEC_EINVAL, "null");
-  if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
-  if (nseg > 0xffffffffull) return set_err(CEC_EINVAL, "too many segments");
+  if (int rc = check_batch(nseg, shard_len)) return rc;
   if (nseg == 0) return CEC_OK;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, hip_stream);
@@ -1645,8 +1657,7 @@ void parity_column(const cec_codec* c, int idx, uint8_t* coef) {
 }
 
 int check_acc_shape(size_t nseg, size_t shard_len) {
-  if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
-  if (nseg > 0xffffffffull) return set_err(CEC_EINVAL, "too many segments");
+  if (int rc = check_batch(nseg, shard_len)) return rc;
   if ((shard_len + 255) / 256 > 0x7fffffffull)
     return set_err(CEC_EINVAL, "shard_len too large (> 512 GiB)");
   return CEC_OK;
@@ -1850,23 +1861,18 @@ int cec_audit_chunks(cec_codec* c, const uint8_t* d_data, const uint8_t* d_parit
 
 int cec_encode(cec_codec* c, uint8_t* const* shards, size_t shard_len) {
   if (!c || !shards) return set_err(CEC_EINVAL, "null");
-  if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
+  if (int rc = check_batch(1, shard_len)) return rc;
   const int n = c->k + c->m;
   for (int i = 0; i < n; ++i)
     if (!shards[i]) return set_err(CEC_EINVAL, "null shard");
   HIP_TRY(hipSetDevice(c->device));
-  const size_t stride = pad256(shard_len);
-  int rc = ensure(&c->stage, &c->stage_bytes, stride * n, c->stream);
+  int rc = stage_ensure(c, n, shard_len);
   if (rc) return rc;
   Layout L = stage_layout(c, shard_len);
-  for (int i = 0; i < c->k; ++i)
-    HIP_TRY(hipMemcpyAsync(c->stage + i * stride, shards[i], shard_len, hipMemcpyHostToDevice,
-                           c->stream));
+  if ((rc = stage_up(c, L.data, shards, c->k, shard_len))) return rc;
   rc = do_encode(c, L, nullptr, 1, c->stream);
   if (rc) return rc;
-  for (int o = 0; o < c->m; ++o)
-    HIP_TRY(hipMemcpyAsync(shards[c->k + o], c->stage + (c->k + o) * stride, shard_len,
-                           hipMemcpyDeviceToHost, c->stream));
+  if ((rc = stage_down(c, shards + c->k, L.parity, c->m, shard_len))) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
   return CEC_OK;
 }
@@ -1874,7 +1880,7 @@ int cec_encode(cec_codec* c, uint8_t* const* shards, size_t shard_len) {
 int cec_reconstruct(cec_codec* c, uint8_t* const* shards, const uint8_t* present,
                     size_t shard_len, int data_only) {
   if (!c || !shards || !present) return set_err(CEC_EINVAL, "null");
-  if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
+  if (int rc = check_batch(1, shard_len)) return rc;
   const int n = c->k + c->m;
   HIP_TRY(hipSetDevice(c->device));
   ProgPtr p;
@@ -1884,21 +1890,19 @@ int cec_reconstruct(cec_codec* c, uint8_t* const* shards, const uint8_t* present
   for (int i = 0; i < n; ++i)
     if (!shards[i]) return set_err(CEC_EINVAL, "null shard");
   const size_t stride = pad256(shard_len);
-  rc = ensure(&c->stage, &c->stage_bytes, stride * n, c->stream);
+  rc = stage_ensure(c, n, shard_len);
   if (rc) return rc;
   Layout L = stage_layout(c, shard_len);
   // Upload only the survivors the plan reads.
   for (int j = 0; j < c->k; ++j) {
     const int i = p->in_idx[j];
-    HIP_TRY(hipMemcpyAsync(c->stage + i * stride, shards[i], shard_len, hipMemcpyHostToDevice,
-                           c->stream));
+    if ((rc = stage_up(c, c->stage + i * stride, shards + i, 1, shard_len))) return rc;
   }
   rc = do_decode(c, *p, L, nullptr, 1, c->stream);
   if (rc) return rc;
   for (int o = 0; o < p->nout; ++o) {
     const int i = p->out_idx[o];
-    HIP_TRY(hipMemcpyAsync(shards[i], c->stage + i * stride, shard_len, hipMemcpyDeviceToHost,
-                           c->stream));
+    if ((rc = stage_down(c, shards + i, c->stage + i * stride, 1, shard_len))) return rc;
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
   evict_decode(c);  // the launch above has completed
@@ -1907,25 +1911,22 @@ int cec_reconstruct(cec_codec* c, uint8_t* const* shards, const uint8_t* present
 
 int cec_verify(cec_codec* c, uint8_t* const* shards, size_t shard_len, int* ok) {
   if (!c || !shards || !ok) return set_err(CEC_EINVAL, "null");
-  if (shard_len == 0) return set_err(CEC_ESHARDLEN, "zero shard length");
+  if (int rc = check_batch(1, shard_len)) return rc;
   const int n = c->k + c->m;
   for (int i = 0; i < n; ++i)
     if (!shards[i]) return set_err(CEC_EINVAL, "null shard");
   HIP_TRY(hipSetDevice(c->device));
-  const size_t stride = pad256(shard_len);
-  int rc = ensure(&c->stage, &c->stage_bytes, stride * n, c->stream);
+  int rc = stage_ensure(c, n, shard_len);
   if (rc) return rc;
   Layout L = stage_layout(c, shard_len);
-  for (int i = 0; i < c->k; ++i)
-    HIP_TRY(hipMemcpyAsync(c->stage + i * stride, shards[i], shard_len, hipMemcpyHostToDevice,
-                           c->stream));
+  if ((rc = stage_up(c, L.data, shards, c->k, shard_len))) return rc;
   rc = do_encode(c, L, nullptr, 1, c->stream);
   if (rc) return rc;
   std::vector<uint8_t> par(shard_len);
+  uint8_t* const host = par.data();
   *ok = 1;
   for (int o = 0; o < c->m && *ok; ++o) {
-    HIP_TRY(hipMemcpyAsync(par.data(), c->stage + (c->k + o) * stride, shard_len,
-                           hipMemcpyDeviceToHost, c->stream));
+    if ((rc = stage_down(c, &host, L.parity + o * L.shard_stride, 1, shard_len))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (std::memcmp(par.data(), shards[c->k + o], shard_len) != 0) *ok = 0;
   }
@@ -1943,13 +1944,11 @@ int cec_encode_idx(cec_codec* c, const uint8_t* data_shard, int idx, uint8_t* co
     if (!parity[o]) return set_err(CEC_EINVAL, "null parity shard");
   HIP_TRY(hipSetDevice(c->device));
   const size_t stride = pad256(shard_len);
-  rc = ensure(&c->stage, &c->stage_bytes, stride * (1 + (size_t)c->m), c->stream);
+  rc = stage_ensure(c, 1 + (size_t)c->m, shard_len);
   if (rc) return rc;
   uint8_t* d_par = c->stage + stride;
-  HIP_TRY(hipMemcpyAsync(c->stage, data_shard, shard_len, hipMemcpyHostToDevice, c->stream));
-  for (int o = 0; o < c->m; ++o)
-    HIP_TRY(hipMemcpyAsync(d_par + o * stride, parity[o], shard_len, hipMemcpyHostToDevice,
-                           c->stream));
+  if ((rc = stage_up(c, c->stage, &data_shard, 1, shard_len))) return rc;
+  if ((rc = stage_up(c, d_par, parity, c->m, shard_len))) return rc;
   uint8_t coef[cec::kMaxShards];
   parity_column(c, idx, coef);
   const uint32_t slot = 0;
@@ -1957,9 +1956,7 @@ int cec_encode_idx(cec_codec* c, const uint8_t* data_shard, int idx, uint8_t* co
                   1, c->stream);
   rc = check_launch();
   if (rc) return rc;
-  for (int o = 0; o < c->m; ++o)
-    HIP_TRY(hipMemcpyAsync(parity[o], d_par + o * stride, shard_len, hipMemcpyDeviceToHost,
-                           c->stream));
+  if ((rc = stage_down(c, parity, d_par, c->m, shard_len))) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
   return CEC_OK;
 }
@@ -1981,30 +1978,24 @@ int cec_update(cec_codec* c, uint8_t* const* shards, const uint8_t* const* new_d
   if (ch.empty()) return CEC_OK;
   HIP_TRY(hipSetDevice(c->device));
   const size_t stride = pad256(shard_len), nc = ch.size();
-  rc = ensure(&c->stage, &c->stage_bytes, stride * (2 * nc + (size_t)c->m), c->stream);
+  rc = stage_ensure(c, 2 * nc + (size_t)c->m, shard_len);
   if (rc) return rc;
   uint8_t* d_new = c->stage + nc * stride;
   uint8_t* d_par = c->stage + 2 * nc * stride;
   std::vector<uint32_t> slots(nc);
   std::vector<uint8_t> coef(nc * c->m);
   for (size_t i = 0; i < nc; ++i) {
-    HIP_TRY(hipMemcpyAsync(c->stage + i * stride, shards[ch[i]], shard_len,
-                           hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_new + i * stride, new_data[ch[i]], shard_len, hipMemcpyHostToDevice,
-                           c->stream));
+    if ((rc = stage_up(c, c->stage + i * stride, shards + ch[i], 1, shard_len))) return rc;
+    if ((rc = stage_up(c, d_new + i * stride, new_data + ch[i], 1, shard_len))) return rc;
     slots[i] = (uint32_t)i;
     parity_column(c, ch[i], &coef[i * c->m]);
   }
-  for (int o = 0; o < c->m; ++o)
-    HIP_TRY(hipMemcpyAsync(d_par + o * stride, shards[c->k + o], shard_len,
-                           hipMemcpyHostToDevice, c->stream));
+  if ((rc = stage_up(c, d_par, shards + c->k, c->m, shard_len))) return rc;
   cec::launch_acc(c->stage, d_new, 0, stride, d_par, 0, stride, shard_len, slots.data(),
                   coef.data(), (int)nc, c->m, true, 1, c->stream);
   rc = check_launch();
   if (rc) return rc;
-  for (int o = 0; o < c->m; ++o)
-    HIP_TRY(hipMemcpyAsync(shards[c->k + o], d_par + o * stride, shard_len,
-                           hipMemcpyDeviceToHost, c->stream));
+  if ((rc = stage_down(c, shards + c->k, d_par, c->m, shard_len))) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
   return CEC_OK;
 }

@@ -50,6 +50,12 @@ struct KernelOpts {
                         // chunks of <= 4 outputs (k_rtb)
   int sha_mode = 0;     // one-shot SHA-256: 0 auto, 1 one wave, 2 two waves per 64 buffers
 };
+// Whether a run-time chunk of bucket `nob` over `nin` inputs takes the bit-plane product (k_rtb,
+// k_ptrb) where one exists for the bucket: asked for, or by default up to four outputs from four
+// or more inputs.
+inline bool rt_takes_rtb(const KernelOpts& o, int nob, int nin) {
+  return o.rt_mode == 3 || (o.rt_mode == 0 && nob <= 4 && nin >= 4);
+}
 // Highest ct_variant this build instantiates (0 in the product library: default only).
 int max_ct_variant();
 

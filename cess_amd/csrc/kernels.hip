@@ -745,23 +745,114 @@ __global__ __launch_bounds__(256) void k_ct_bytes(Layout L, const uint32_t* __re
 // Program chunks are read through the constant address space: they are never written while a
 // kernel runs, so uniform-address loads become s_load (SGPR results, SALU mask expansion).
 typedef const uint32_t __attribute__((address_space(4))) cu32;
+typedef const uint64_t __attribute__((address_space(4))) cu64;
 __device__ __forceinline__ const cu32* as_const(const uint32_t* p) {
   return (const cu32*)(uintptr_t)p;
 }
 
-template <int NOB, int U, class TV, class T, class LD>
+__device__ __forceinline__ const uint32_t* as_const_ptr(const uint32_t* const* a, uint32_t y) {
+  return (const uint32_t*)(uintptr_t)((const cu64*)(uintptr_t)a)[y];
+}
+
+// Pointer-table rows (see "Pointer-table addressing" below) are read through the constant address
+// space too, and their words are turned into address_space(1) pointers, not generic ones: the
+// accesses stay global_load / global_store (a flat access counts on lgkmcnt too and would
+// serialise with the scalar reads, see shard_ptr_sel).
+typedef uint8_t __attribute__((address_space(1))) gu8;
+
+__device__ __forceinline__ const cu64* tab_row(const uint64_t* tab, uint64_t row, uint32_t rs) {
+  return (const cu64*)(uintptr_t)tab + row * rs;
+}
+__device__ __forceinline__ gu8* gptr(uint64_t a) { return (gu8*)a; }
+
+template <bool NT, class TV>
+__device__ __forceinline__ TV gld(const gu8* p) {
+  typedef const TV __attribute__((address_space(1))) G;
+  if constexpr (NT) return __builtin_nontemporal_load((G*)p);
+  else return *(G*)p;
+}
+template <bool NT, class TV>
+__device__ __forceinline__ void gst(gu8* p, TV v) {
+  typedef TV __attribute__((address_space(1))) G;
+  if constexpr (NT) __builtin_nontemporal_store(v, (G*)p);
+  else *(G*)p = v;
+}
+
+// One column access for either pointer kind.
+template <bool NT, class TV>
+__device__ __forceinline__ TV ldv(const uint8_t* p) { return ld16<NT, TV>(p); }
+template <bool NT, class TV>
+__device__ __forceinline__ TV ldv(const gu8* p) { return gld<NT, TV>(p); }
+template <bool NT, class TV>
+__device__ __forceinline__ void stv(uint8_t* p, TV v) { st16<NT, TV>(p, v); }
+template <bool NT, class TV>
+__device__ __forceinline__ void stv(gu8* p, TV v) { gst<NT, TV>(p, v); }
+
+// Where a workgroup row of the run-time products finds its program chunk P and its shards: key(j)
+// names input j of the program, in(key) / out(o) give a shard's address. The index type of key
+// is the caller's: the address arithmetic of the two products differs in it (32-bit in rt_body,
+// widened first in rtb_body) and the scalar code the compiler makes of each depends on it.
+// `Arg` is how the product bodies take the policy. Both forms are the ones that compile to the
+// code the kernels had with the addressing written into them.
+// Batch layout: row y is listed segment y (or y itself) with the launch's chunk, or with its own;
+// the chunk's index arrays (in[256] at word 4, out[256] behind it) name shards of the Layout. The
+// Layout is held by value and the policy passed by value: through a reference to the kernel's
+// argument the in-layout kernels lose their scalar address arithmetic.
+struct BatchAddr {
+  using Arg = const BatchAddr;
+  Layout L;
+  const cu32* __restrict__ P;
+  uint32_t seg;
+  __device__ __forceinline__ BatchAddr(const Layout& L_, const uint32_t* chunk,
+                                       const uint32_t* const* per_seg, const uint32_t* seg_list,
+                                       uint32_t y)
+      : L(L_) {
+    seg = seg_list ? seg_list[y] : y;
+    P = as_const(per_seg ? as_const_ptr(per_seg, y) : chunk);
+  }
+  __device__ __forceinline__ uint64_t len() const { return L.len; }
+  template <class I>
+  __device__ __forceinline__ uint32_t key(I j) const { return P[4 + j]; }
+  __device__ __forceinline__ uint8_t* in(uint32_t key) const { return shard_ptr(L, (int)key, seg); }
+  __device__ __forceinline__ uint8_t* out(int o) const {
+    return shard_ptr(L, (int)P[4 + 256 + o], seg);
+  }
+};
+// Table row: {program chunk, nin inputs, nout outputs} in the chunk's order (its in / out index
+// arrays are not read: the row already is in program order), so input j is addressed by position.
+struct TableAddr {
+  using Arg = const TableAddr&;
+  const cu32* __restrict__ P;
+  const cu64* __restrict__ ins;
+  const cu64* __restrict__ outs;
+  uint64_t n;
+  __device__ __forceinline__ TableAddr(const uint64_t* tab, uint64_t r, uint32_t rs, uint64_t len) {
+    const cu64* __restrict__ row = tab_row(tab, r, rs);
+    P = as_const((const uint32_t*)(uintptr_t)row[0]);
+    ins = row + 1;
+    outs = ins + P[0];
+    n = len;
+  }
+  __device__ __forceinline__ uint64_t len() const { return n; }
+  template <class I>
+  __device__ __forceinline__ uint32_t key(I j) const { return (uint32_t)j; }
+  __device__ __forceinline__ gu8* in(uint32_t key) const { return gptr(ins[key]); }
+  __device__ __forceinline__ gu8* out(int o) const { return gptr(outs[o]); }
+};
+
+template <int NOB, int U, class TV, class T, class Addr, class LD>
 __device__ __forceinline__ void rt_accumulate(T (&acc)[NOB][U], const cu32* __restrict__ P,
-                                              LD ld) {
+                                              const Addr& a, LD ld) {
   const uint32_t nin = P[0];
   const cu32* __restrict__ hbs = P + 4 + 512;
   const cu32* __restrict__ masks = P + kRtHeaderWords;
   T cur[U], nxt[U];
 #pragma unroll
-  for (int u = 0; u < U; ++u) cur[u] = ld(P[4], u);
+  for (int u = 0; u < U; ++u) cur[u] = ld(a.key(0), u);
   for (uint32_t j = 0; j < nin; ++j) {
     if (j + 1 < nin) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) nxt[u] = ld(P[4 + j + 1], u);
+      for (int u = 0; u < U; ++u) nxt[u] = ld(a.key(j + 1), u);
     }
     const int hb = (int)hbs[j];
     T p[U];
@@ -799,61 +890,53 @@ __device__ __forceinline__ uint8_t* shard_ptr_sel(const Layout& L, uint32_t idx,
   return base + seg * sstr + (uint64_t)j * L.shard_stride;
 }
 
-__device__ __forceinline__ const uint32_t* as_const_ptr(const uint32_t* const* a, uint32_t y) {
-  typedef const uint64_t __attribute__((address_space(4))) cu64;
-  return (const uint32_t*)(uintptr_t)((const cu64*)(uintptr_t)a)[y];
-}
-
-template <int NOB, int U, class TV>
-__global__ __launch_bounds__(256) void k_rt(Layout L, const uint32_t* __restrict__ chunk,
-                                            const uint32_t* const* __restrict__ per_seg,
-                                            const uint32_t* __restrict__ seg_list, uint32_t seg0,
-                                            int vec_ok) {
-  const uint32_t y = seg0 + blockIdx.y;
-  const uint32_t seg = seg_list ? seg_list[y] : y;
-  const cu32* __restrict__ P = as_const(per_seg ? as_const_ptr(per_seg, y) : chunk);
+// The per-bit mask product of one workgroup over program chunk P: any output count up to the
+// bucket NOB, U columns of TV per lane.
+template <int NOB, int U, class TV, class Addr>
+__device__ __forceinline__ void rt_body(typename Addr::Arg a, int vec_ok) {
+  const cu32* __restrict__ P = a.P;
   const uint32_t nout = P[1];
-  const cu32* __restrict__ out_idx = P + 4 + 256;
+  const uint64_t len = a.len();
   constexpr int VB = sizeof(TV);
   if (vec_ok) {
-    const uint64_t nvec = L.len / VB;
+    const uint64_t nvec = len / VB;
     const uint64_t base = (uint64_t)blockIdx.x * (256 * U) + threadIdx.x;
     TV acc[NOB][U];
 #pragma unroll
     for (int o = 0; o < NOB; ++o)
 #pragma unroll
       for (int u = 0; u < U; ++u) acc[o][u] = TV(0);
-    auto ld = [&](uint32_t sh, int u) CEC_AI -> TV {
+    auto ld = [&](uint32_t key, int u) CEC_AI -> TV {
       const uint64_t v = base + u * 256;
       if (v >= nvec) return TV(0);
-      return ld16<false, TV>(shard_ptr(L, (int)sh, seg) + v * VB);
+      return ldv<false, TV>(a.in(key) + v * VB);
     };
-    rt_accumulate<NOB, U, TV>(acc, P, ld);
+    rt_accumulate<NOB, U, TV>(acc, P, a, ld);
 #pragma unroll
     for (int o = 0; o < NOB; ++o) {
       if (o < (int)nout) {
-        uint8_t* dst = shard_ptr(L, (int)out_idx[o], seg);
+        auto* dst = a.out(o);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const uint64_t v = base + u * 256;
-          if (v < nvec) st16<false, TV>(dst + v * VB, acc[o][u]);
+          if (v < nvec) stv<false, TV>(dst + v * VB, acc[o][u]);
         }
       }
     }
-    if (!(L.len % VB) || blockIdx.x != gridDim.x - 1) return;
+    if (!(len % VB) || blockIdx.x != gridDim.x - 1) return;
   }
   // byte path: whole shard (vec_ok == 0, grid covers len) or the tail (last block)
-  const uint64_t i = vec_ok ? (L.len - L.len % VB) + threadIdx.x
+  const uint64_t i = vec_ok ? (len - len % VB) + threadIdx.x
                             : (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= L.len) return;
+  if (i >= len) return;
   uint32_t acc[NOB][1];
 #pragma unroll
   for (int o = 0; o < NOB; ++o) acc[o][0] = 0;
-  auto ld = [&](uint32_t sh, int) CEC_AI -> uint32_t { return shard_ptr(L, (int)sh, seg)[i]; };
-  rt_accumulate<NOB, 1, uint32_t>(acc, P, ld);
+  auto ld = [&](uint32_t key, int) CEC_AI -> uint32_t { return a.in(key)[i]; };
+  rt_accumulate<NOB, 1, uint32_t>(acc, P, a, ld);
 #pragma unroll
   for (int o = 0; o < NOB; ++o)
-    if (o < (int)nout) shard_ptr(L, (int)out_idx[o], seg)[i] = (uint8_t)acc[o][0];
+    if (o < (int)nout) a.out(o)[i] = (uint8_t)acc[o][0];
 }
 
 // Bit-plane run-time matvec for few outputs (k_rtb): per output o and coefficient bit b one
@@ -863,31 +946,25 @@ __global__ __launch_bounds__(256) void k_rt(Layout L, const uint32_t* __restrict
 // stream through (the next column's load is issued before the current one is folded in), so the
 // registers are the 8 * NOB accumulators: decode of a few lost fragments of a wide code (the
 // restoral case) and partial rebuilds, where nout << nin.
-template <int NOB, class TV, int PF>
-__global__ __launch_bounds__(256) void k_rtb(Layout L, const uint32_t* __restrict__ chunk,
-                                             const uint32_t* const* __restrict__ per_seg,
-                                             const uint32_t* __restrict__ seg_list, uint32_t seg0,
-                                             int vec_ok) {
-  const uint32_t y = seg0 + blockIdx.y;
-  const uint32_t seg = seg_list ? seg_list[y] : y;
-  const cu32* __restrict__ P = as_const(per_seg ? as_const_ptr(per_seg, y) : chunk);
+template <int NOB, class TV, int PF, class Addr>
+__device__ __forceinline__ void rtb_body(typename Addr::Arg a, int vec_ok) {
+  const cu32* __restrict__ P = a.P;
   const uint32_t nin = P[0], nout = P[1];
-  const cu32* __restrict__ in_idx = P + 4;
-  const cu32* __restrict__ out_idx = P + 4 + 256;
+  const uint64_t len = a.len();
   const cu32* __restrict__ masks = P + kRtHeaderWords;
   // inputs stream through a ring of PF columns: column j + PF is loaded while column j folds
   auto fold = [&]<class T>(T (&t)[NOB][8], auto ld) CEC_AI {
     T ring[PF];
 #pragma unroll
     for (int q = 0; q < PF; ++q)
-      if (q < (int)nin) ring[q] = ld(in_idx[q]);
+      if (q < (int)nin) ring[q] = ld(a.key((uint64_t)q));
     for (uint32_t j0 = 0; j0 < nin; j0 += PF) {
 #pragma unroll
       for (int q = 0; q < PF; ++q) {
         const uint32_t j = j0 + q;
         if (j >= nin) break;  // wave-uniform
         const T cur = ring[q];
-        if (j + PF < nin) ring[q] = ld(in_idx[j + PF]);
+        if (j + PF < nin) ring[q] = ld(a.key((uint64_t)(j + PF)));
         // all 8 bits, no branch on the column's top bit: the 8 * NOB masks of a column then
         // come in as one wide scalar load
         const cu32* __restrict__ mk = masks + j * 8 * NOB;
@@ -907,32 +984,49 @@ __global__ __launch_bounds__(256) void k_rtb(Layout L, const uint32_t* __restric
   constexpr int VB = sizeof(TV);
   if (vec_ok) {
     const uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v < L.len / VB) {
+    if (v < len / VB) {
       TV t[NOB][8];
 #pragma unroll
       for (int o = 0; o < NOB; ++o)
 #pragma unroll
         for (int b = 0; b < 8; ++b) t[o][b] = TV(0);
-      fold(t, [&](uint32_t sh) CEC_AI { return ld16<true, TV>(shard_ptr(L, (int)sh, seg) + v * VB); });
+      fold(t, [&](uint32_t key) CEC_AI { return ldv<true, TV>(a.in(key) + v * VB); });
 #pragma unroll
       for (int o = 0; o < NOB; ++o)
-        if (o < (int)nout) st16<true, TV>(shard_ptr(L, (int)out_idx[o], seg) + v * VB, horner(t[o]));
+        if (o < (int)nout) stv<true, TV>(a.out(o) + v * VB, horner(t[o]));
     }
-    if (!(L.len % VB) || blockIdx.x != gridDim.x - 1) return;
+    if (!(len % VB) || blockIdx.x != gridDim.x - 1) return;
   }
   // byte path: whole shard (vec_ok == 0, grid covers len) or the tail (last block)
-  const uint64_t i = vec_ok ? (L.len - L.len % VB) + threadIdx.x
+  const uint64_t i = vec_ok ? (len - len % VB) + threadIdx.x
                             : (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= L.len) return;
+  if (i >= len) return;
   uint32_t t[NOB][8];
 #pragma unroll
   for (int o = 0; o < NOB; ++o)
 #pragma unroll
     for (int b = 0; b < 8; ++b) t[o][b] = 0;
-  fold(t, [&](uint32_t sh) CEC_AI -> uint32_t { return shard_ptr(L, (int)sh, seg)[i]; });
+  fold(t, [&](uint32_t key) CEC_AI -> uint32_t { return a.in(key)[i]; });
 #pragma unroll
   for (int o = 0; o < NOB; ++o)
-    if (o < (int)nout) shard_ptr(L, (int)out_idx[o], seg)[i] = (uint8_t)horner(t[o]);
+    if (o < (int)nout) a.out(o)[i] = (uint8_t)horner(t[o]);
+}
+
+// The in-layout entry points (the pointer-table ones, k_ptrt and k_ptrb, are further down).
+template <int NOB, int U, class TV>
+__global__ __launch_bounds__(256) void k_rt(Layout L, const uint32_t* __restrict__ chunk,
+                                            const uint32_t* const* __restrict__ per_seg,
+                                            const uint32_t* __restrict__ seg_list, uint32_t seg0,
+                                            int vec_ok) {
+  rt_body<NOB, U, TV, BatchAddr>(BatchAddr(L, chunk, per_seg, seg_list, seg0 + blockIdx.y), vec_ok);
+}
+
+template <int NOB, class TV, int PF>
+__global__ __launch_bounds__(256) void k_rtb(Layout L, const uint32_t* __restrict__ chunk,
+                                             const uint32_t* const* __restrict__ per_seg,
+                                             const uint32_t* __restrict__ seg_list, uint32_t seg0,
+                                             int vec_ok) {
+  rtb_body<NOB, TV, PF, BatchAddr>(BatchAddr(L, chunk, per_seg, seg_list, seg0 + blockIdx.y), vec_ok);
 }
 
 // Horner over input groups with run-time coefficients (k_rth): the compile-time k_hg scheme
@@ -1251,6 +1345,49 @@ void for_seg_chunks(uint32_t nseg, F f) {
   for (uint32_t s0 = 0; s0 < nseg; s0 += kMaxGridY) f(s0, nseg - s0 < kMaxGridY ? nseg - s0 : kMaxGridY);
 }
 
+// Grid width of the run-time and pointer-table kernels: blocks of 256 lanes with `u` columns of
+// `vb` bytes each (the last block also takes the tail), or of 256 bytes on the all-byte path.
+unsigned rt_grid_x(uint64_t len, size_t vb, int u, bool vec_ok) {
+  const uint64_t gx = vec_ok ? (len / vb + 256 * u - 1) / (256 * u) : (len + 255) / 256;
+  return gx ? (unsigned)gx : 1u;
+}
+
+// The tuned shapes of the run-time products by output bucket, in-layout and pointer-table alike:
+// f is called with the bucket's shape tag.
+template <int NOB, int U, class TV>
+struct RtShape {};  // k_rt / k_ptrt: U columns of TV per lane
+template <class F>
+void rt_dispatch(int nob, F f) {
+  switch (nob) {
+    case 1: f(RtShape<1, 1, u32x4>{}); break;
+    case 2: f(RtShape<2, 1, u32x4>{}); break;
+    case 3: f(RtShape<3, 1, u32x4>{}); break;
+    case 4: f(RtShape<4, 1, u32x4>{}); break;
+    case 5: f(RtShape<5, 1, u32x4>{}); break;
+    case 6: f(RtShape<6, 1, u32x4>{}); break;
+    case 7: f(RtShape<7, 1, u32x2>{}); break;
+    case 8: f(RtShape<8, 1, u32x2>{}); break;
+    case 12: f(RtShape<12, 1, u32x2>{}); break;
+    case 16: f(RtShape<16, 1, uint32_t>{}); break;
+    case 24: f(RtShape<24, 1, uint32_t>{}); break;
+    default: f(RtShape<32, 1, uint32_t>{}); break;
+  }
+}
+template <int NOB, class TV, int PF>
+struct RtbShape {};  // k_rtb / k_ptrb: columns of TV, PF input columns in flight
+template <class F>
+bool rtb_dispatch(int nob, F f) {  // false (f not called) for a bucket wider than four
+  switch (nob) {
+    // 8-byte columns, several in flight (profiles/r02/rtb_sweep.txt: one output u32x4 PF1 ->
+    // u32x2 PF4 0.199 -> 0.184 ms, four outputs PF4 -> PF8 0.296 -> 0.291)
+    case 1: f(RtbShape<1, u32x2, 4>{}); return true;
+    case 2: f(RtbShape<2, u32x2, 4>{}); return true;
+    case 3: f(RtbShape<3, u32x2, 4>{}); return true;
+    case 4: f(RtbShape<4, u32x2, 8>{}); return true;
+  }
+  return false;
+}
+
 template <class P, int U, bool NT, class TV = u32x4, int PF = 1, bool WIN = false, int BS = 256>
 void run_ct(const Layout& L, const uint32_t* seg_list, uint32_t nseg, hipStream_t st) {
   if (layout_vec16_ok(L)) {
@@ -1511,31 +1648,19 @@ template <int NOB, int U, class TV>
 void run_rt(const Layout& L, const uint32_t* chunk, const uint32_t* const* per_seg,
             const uint32_t* seg_list, uint32_t nseg, hipStream_t st) {
   const int vec_ok = layout_vec16_ok(L) ? 1 : 0;
-  uint64_t gx = vec_ok ? (L.len / sizeof(TV) + 256 * U - 1) / (256 * U) : (L.len + 255) / 256;
-  if (gx == 0) gx = 1;
+  const unsigned gx = rt_grid_x(L.len, sizeof(TV), U, vec_ok);
   for_seg_chunks(nseg, [&](uint32_t s0, uint32_t ny) {
-    hipLaunchKernelGGL((k_rt<NOB, U, TV>), dim3((unsigned)gx, ny), dim3(256), 0, st, L, chunk,
-                       per_seg, seg_list, s0, vec_ok);
+    hipLaunchKernelGGL((k_rt<NOB, U, TV>), dim3(gx, ny), dim3(256), 0, st, L, chunk, per_seg,
+                       seg_list, s0, vec_ok);
   });
 }
 }  // namespace
 
 void launch_matvec_rt(const Layout& L, const uint32_t* chunk, const uint32_t* const* per_seg,
                       int nob, const uint32_t* seg_list, uint32_t nseg, hipStream_t st) {
-  switch (nob) {
-    case 1: run_rt<1, 1, u32x4>(L, chunk, per_seg, seg_list, nseg, st); break;
-    case 2: run_rt<2, 1, u32x4>(L, chunk, per_seg, seg_list, nseg, st); break;
-    case 3: run_rt<3, 1, u32x4>(L, chunk, per_seg, seg_list, nseg, st); break;
-    case 4: run_rt<4, 1, u32x4>(L, chunk, per_seg, seg_list, nseg, st); break;
-    case 5: run_rt<5, 1, u32x4>(L, chunk, per_seg, seg_list, nseg, st); break;
-    case 6: run_rt<6, 1, u32x4>(L, chunk, per_seg, seg_list, nseg, st); break;
-    case 7: run_rt<7, 1, u32x2>(L, chunk, per_seg, seg_list, nseg, st); break;
-    case 8: run_rt<8, 1, u32x2>(L, chunk, per_seg, seg_list, nseg, st); break;
-    case 12: run_rt<12, 1, u32x2>(L, chunk, per_seg, seg_list, nseg, st); break;
-    case 16: run_rt<16, 1, uint32_t>(L, chunk, per_seg, seg_list, nseg, st); break;
-    case 24: run_rt<24, 1, uint32_t>(L, chunk, per_seg, seg_list, nseg, st); break;
-    default: run_rt<32, 1, uint32_t>(L, chunk, per_seg, seg_list, nseg, st); break;
-  }
+  rt_dispatch(nob, [&]<int NOB, int U, class TV>(RtShape<NOB, U, TV>) {
+    run_rt<NOB, U, TV>(L, chunk, per_seg, seg_list, nseg, st);
+  });
 }
 
 namespace {
@@ -1543,11 +1668,10 @@ template <int NOB, class TV, int PF>
 void run_rtb(const Layout& L, const uint32_t* chunk, const uint32_t* const* per_seg,
              const uint32_t* seg_list, uint32_t nseg, hipStream_t st) {
   const int vec_ok = layout_vec16_ok(L) ? 1 : 0;
-  uint64_t gx = vec_ok ? (L.len / sizeof(TV) + 255) / 256 : (L.len + 255) / 256;
-  if (gx == 0) gx = 1;
+  const unsigned gx = rt_grid_x(L.len, sizeof(TV), 1, vec_ok);
   for_seg_chunks(nseg, [&](uint32_t s0, uint32_t ny) {
-    hipLaunchKernelGGL((k_rtb<NOB, TV, PF>), dim3((unsigned)gx, ny), dim3(256), 0, st, L, chunk,
-                       per_seg, seg_list, s0, vec_ok);
+    hipLaunchKernelGGL((k_rtb<NOB, TV, PF>), dim3(gx, ny), dim3(256), 0, st, L, chunk, per_seg,
+                       seg_list, s0, vec_ok);
   });
 }
 }  // namespace
@@ -1587,15 +1711,9 @@ bool launch_matvec_rtb(const Layout& L, const uint32_t* chunk, const uint32_t* c
 #else
   (void)variant;
 #endif
-  switch (nob) {
-    // 8-byte columns, several in flight (profiles/r02/rtb_sweep.txt: one output u32x4 PF1 ->
-    // u32x2 PF4 0.199 -> 0.184 ms, four outputs PF4 -> PF8 0.296 -> 0.291)
-    case 1: run_rtb<1, u32x2, 4>(L, chunk, per_seg, seg_list, nseg, st); return true;
-    case 2: run_rtb<2, u32x2, 4>(L, chunk, per_seg, seg_list, nseg, st); return true;
-    case 3: run_rtb<3, u32x2, 4>(L, chunk, per_seg, seg_list, nseg, st); return true;
-    case 4: run_rtb<4, u32x2, 8>(L, chunk, per_seg, seg_list, nseg, st); return true;
-  }
-  return false;
+  return rtb_dispatch(nob, [&]<int NOB, class TV, int PF>(RtbShape<NOB, TV, PF>) {
+    run_rtb<NOB, TV, PF>(L, chunk, per_seg, seg_list, nseg, st);
+  });
 }
 
 namespace {
@@ -1654,31 +1772,9 @@ void launch_fill_splitmix(uint8_t* out, uint64_t seg_bytes, uint64_t nseg, uint6
 // Scattered shards: every workgroup row (blockIdx.y) owns one row of 64-bit words in a device
 // table, the addresses of its inputs in program order, then of its outputs. The row is read
 // through the constant address space like the program chunks, so the addresses arrive as
-// wave-uniform scalar loads ahead of the global loads, and they are turned into address_space(1)
-// pointers, not generic ones: the accesses stay global_load / global_store (a flat access counts
-// on lgkmcnt too and would serialise with the scalar reads, see shard_ptr_sel). The column bodies
-// are those of the in-layout kernels (ct_column_*, the k_rt and k_rtb products); only the
-// addressing differs. `vec_ok` is per call: every address of the table is 16-byte aligned.
-typedef const uint64_t __attribute__((address_space(4))) cu64;
-typedef uint8_t __attribute__((address_space(1))) gu8;
-
-__device__ __forceinline__ const cu64* tab_row(const uint64_t* tab, uint64_t row, uint32_t rs) {
-  return (const cu64*)(uintptr_t)tab + row * rs;
-}
-__device__ __forceinline__ gu8* gptr(uint64_t a) { return (gu8*)a; }
-
-template <bool NT, class TV>
-__device__ __forceinline__ TV gld(const gu8* p) {
-  typedef const TV __attribute__((address_space(1))) G;
-  if constexpr (NT) return __builtin_nontemporal_load((G*)p);
-  else return *(G*)p;
-}
-template <bool NT, class TV>
-__device__ __forceinline__ void gst(gu8* p, TV v) {
-  typedef TV __attribute__((address_space(1))) G;
-  if constexpr (NT) __builtin_nontemporal_store(v, (G*)p);
-  else *(G*)p = v;
-}
+// wave-uniform scalar loads ahead of the global loads (tab_row, gptr, gld / gst above). The column
+// bodies are those of the in-layout kernels (ct_column_*, rt_body, rtb_body); only the addressing
+// differs. `vec_ok` is per call: every address of the table is 16-byte aligned.
 
 // RS(2,1) with compile-time coefficients: row = {input 0, input 1, output, case}; case 0 / 1 =
 // the closed-form rebuild of data fragment 0 / 1 (inputs: the other data fragment, the parity),
@@ -1731,228 +1827,49 @@ __global__ __launch_bounds__(256) void k_ptr21(const uint64_t* __restrict__ tab,
   else if (e == 2) ptr_tile21<EncCT<2, 1>, NT>(i0, i1, o0, len, vec_ok);
 }
 
-// Run-time coefficients: row = {program chunk, nin inputs, nout outputs} in the chunk's order
-// (its in / out index arrays are not read: the row already is in program order), rows of a launch
-// `rs` words apart. k_rt's product (rt_accumulate) with input j addressed by position.
-template <int NOB, int U, class TV, class T, class LD>
-__device__ __forceinline__ void rt_accumulate_tab(T (&acc)[NOB][U], const cu32* __restrict__ P,
-                                                  LD ld) {
-  const uint32_t nin = P[0];
-  const cu32* __restrict__ hbs = P + 4 + 512;
-  const cu32* __restrict__ masks = P + kRtHeaderWords;
-  T cur[U], nxt[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) cur[u] = ld(0u, u);
-  for (uint32_t j = 0; j < nin; ++j) {
-    if (j + 1 < nin) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) nxt[u] = ld(j + 1, u);
-    }
-    const int hb = (int)hbs[j];
-    T p[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) p[u] = cur[u];
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      if (b > hb) break;  // wave-uniform: no higher coefficient bit in this column
-      if (b > 0) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) p[u] = xt(p[u]);
-      }
-      const cu32* __restrict__ mk = masks + (j * 8 + b) * NOB;
-#pragma unroll
-      for (int o = 0; o < NOB; ++o) {
-        const uint32_t m = mk[o];
-#pragma unroll
-        for (int u = 0; u < U; ++u) acc[o][u] = bitop3_xand(acc[o][u], p[u], m);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) cur[u] = nxt[u];
-  }
-}
-
-// The general form (k_rt with table addressing): any output count up to the bucket NOB.
+// Run-time coefficients: row = {program chunk, nin inputs, nout outputs} (TableAddr), rows of a
+// launch `rs` words apart. k_ptrt is k_rt's product, k_ptrb k_rtb's.
 template <int NOB, int U, class TV>
 __global__ __launch_bounds__(256) void k_ptrt(const uint64_t* __restrict__ tab, uint32_t row0,
                                               uint32_t rs, uint64_t len, int vec_ok) {
-  const cu64* __restrict__ row = tab_row(tab, row0 + blockIdx.y, rs);
-  const cu32* __restrict__ P = as_const((const uint32_t*)(uintptr_t)row[0]);
-  const uint32_t nin = P[0], nout = P[1];
-  const cu64* __restrict__ in = row + 1;
-  const cu64* __restrict__ out = in + nin;
-  constexpr int VB = sizeof(TV);
-  if (vec_ok) {
-    const uint64_t nvec = len / VB;
-    const uint64_t base = (uint64_t)blockIdx.x * (256 * U) + threadIdx.x;
-    TV acc[NOB][U];
-#pragma unroll
-    for (int o = 0; o < NOB; ++o)
-#pragma unroll
-      for (int u = 0; u < U; ++u) acc[o][u] = TV(0);
-    auto ld = [&](uint32_t j, int u) CEC_AI -> TV {
-      const uint64_t v = base + u * 256;
-      if (v >= nvec) return TV(0);
-      return gld<false, TV>(gptr(in[j]) + v * VB);
-    };
-    rt_accumulate_tab<NOB, U, TV>(acc, P, ld);
-#pragma unroll
-    for (int o = 0; o < NOB; ++o) {
-      if (o < (int)nout) {
-        gu8* dst = gptr(out[o]);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const uint64_t v = base + u * 256;
-          if (v < nvec) gst<false, TV>(dst + v * VB, acc[o][u]);
-        }
-      }
-    }
-    if (!(len % VB) || blockIdx.x != gridDim.x - 1) return;
-  }
-  // byte path: whole shard (vec_ok == 0, grid covers len) or the tail (last block)
-  const uint64_t i = vec_ok ? (len - len % VB) + threadIdx.x
-                            : (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= len) return;
-  uint32_t acc[NOB][1];
-#pragma unroll
-  for (int o = 0; o < NOB; ++o) acc[o][0] = 0;
-  auto ld = [&](uint32_t j, int) CEC_AI -> uint32_t { return gptr(in[j])[i]; };
-  rt_accumulate_tab<NOB, 1, uint32_t>(acc, P, ld);
-#pragma unroll
-  for (int o = 0; o < NOB; ++o)
-    if (o < (int)nout) gptr(out[o])[i] = (uint8_t)acc[o][0];
+  rt_body<NOB, U, TV, TableAddr>(TableAddr(tab, row0 + blockIdx.y, rs, len), vec_ok);
 }
 
-// The bit-plane form for few outputs (k_rtb with table addressing): 8 * NOB accumulators, the
-// inputs stream through a ring of PF columns.
 template <int NOB, class TV, int PF>
 __global__ __launch_bounds__(256) void k_ptrb(const uint64_t* __restrict__ tab, uint32_t row0,
                                               uint32_t rs, uint64_t len, int vec_ok) {
-  const cu64* __restrict__ row = tab_row(tab, row0 + blockIdx.y, rs);
-  const cu32* __restrict__ P = as_const((const uint32_t*)(uintptr_t)row[0]);
-  const uint32_t nin = P[0], nout = P[1];
-  const cu64* __restrict__ in = row + 1;
-  const cu64* __restrict__ out = in + nin;
-  const cu32* __restrict__ masks = P + kRtHeaderWords;
-  auto fold = [&]<class T>(T (&t)[NOB][8], auto ld) CEC_AI {
-    T ring[PF];
-#pragma unroll
-    for (int q = 0; q < PF; ++q)
-      if (q < (int)nin) ring[q] = ld((uint32_t)q);
-    for (uint32_t j0 = 0; j0 < nin; j0 += PF) {
-#pragma unroll
-      for (int q = 0; q < PF; ++q) {
-        const uint32_t j = j0 + q;
-        if (j >= nin) break;  // wave-uniform
-        const T cur = ring[q];
-        if (j + PF < nin) ring[q] = ld(j + PF);
-        const cu32* __restrict__ mk = masks + j * 8 * NOB;
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-#pragma unroll
-          for (int o = 0; o < NOB; ++o) t[o][b] = bitop3_xand(t[o][b], cur, mk[b * NOB + o]);
-      }
-    }
-  };
-  auto horner = [&]<class T>(const T (&t)[8]) CEC_AI -> T {
-    T r = t[7];
-#pragma unroll
-    for (int b = 6; b >= 0; --b) r = xt(r) ^ t[b];
-    return r;
-  };
-  constexpr int VB = sizeof(TV);
-  if (vec_ok) {
-    const uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v < len / VB) {
-      TV t[NOB][8];
-#pragma unroll
-      for (int o = 0; o < NOB; ++o)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) t[o][b] = TV(0);
-      fold(t, [&](uint32_t j) CEC_AI { return gld<true, TV>(gptr(in[j]) + v * VB); });
-#pragma unroll
-      for (int o = 0; o < NOB; ++o)
-        if (o < (int)nout) gst<true, TV>(gptr(out[o]) + v * VB, horner(t[o]));
-    }
-    if (!(len % VB) || blockIdx.x != gridDim.x - 1) return;
-  }
-  // byte path: whole shard (vec_ok == 0, grid covers len) or the tail (last block)
-  const uint64_t i = vec_ok ? (len - len % VB) + threadIdx.x
-                            : (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= len) return;
-  uint32_t t[NOB][8];
-#pragma unroll
-  for (int o = 0; o < NOB; ++o)
-#pragma unroll
-    for (int b = 0; b < 8; ++b) t[o][b] = 0;
-  fold(t, [&](uint32_t j) CEC_AI -> uint32_t { return gptr(in[j])[i]; });
-#pragma unroll
-  for (int o = 0; o < NOB; ++o)
-    if (o < (int)nout) gptr(out[o])[i] = (uint8_t)horner(t[o]);
+  rtb_body<NOB, TV, PF, TableAddr>(TableAddr(tab, row0 + blockIdx.y, rs, len), vec_ok);
 }
-
-namespace {
-template <int NOB, int U, class TV>
-void run_ptrt(const uint64_t* tab, uint32_t nrows, uint32_t rs, uint64_t len, int vec_ok,
-              hipStream_t st) {
-  uint64_t gx = vec_ok ? (len / sizeof(TV) + 256 * U - 1) / (256 * U) : (len + 255) / 256;
-  if (gx == 0) gx = 1;
-  for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
-    hipLaunchKernelGGL((k_ptrt<NOB, U, TV>), dim3((unsigned)gx, ny), dim3(256), 0, st, tab, r0, rs,
-                       len, vec_ok);
-  });
-}
-template <int NOB, class TV, int PF>
-void run_ptrb(const uint64_t* tab, uint32_t nrows, uint32_t rs, uint64_t len, int vec_ok,
-              hipStream_t st) {
-  uint64_t gx = vec_ok ? (len / sizeof(TV) + 255) / 256 : (len + 255) / 256;
-  if (gx == 0) gx = 1;
-  for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
-    hipLaunchKernelGGL((k_ptrb<NOB, TV, PF>), dim3((unsigned)gx, ny), dim3(256), 0, st, tab, r0, rs,
-                       len, vec_ok);
-  });
-}
-}  // namespace
 
 void launch_ptrs_rs21(const uint64_t* tab, uint32_t nrows, uint64_t len, bool vec_ok,
                       hipStream_t st) {
-  uint64_t gx = vec_ok ? (len / 16 + 255) / 256 : (len + 255) / 256;
-  if (gx == 0) gx = 1;
+  const unsigned gx = rt_grid_x(len, 16, 1, vec_ok);
   for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
-    hipLaunchKernelGGL((k_ptr21<true>), dim3((unsigned)gx, ny), dim3(256), 0, st, tab, r0, len,
+    hipLaunchKernelGGL((k_ptr21<true>), dim3(gx, ny), dim3(256), 0, st, tab, r0, len,
                        vec_ok ? 1 : 0);
   });
 }
 
 bool launch_ptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
                      bool vec_ok, hipStream_t st) {
-  const int v = vec_ok ? 1 : 0;
-  switch (nob) {  // the column widths and ring depths of launch_matvec_rtb
-    case 1: run_ptrb<1, u32x2, 4>(tab, nrows, rs, len, v, st); return true;
-    case 2: run_ptrb<2, u32x2, 4>(tab, nrows, rs, len, v, st); return true;
-    case 3: run_ptrb<3, u32x2, 4>(tab, nrows, rs, len, v, st); return true;
-    case 4: run_ptrb<4, u32x2, 8>(tab, nrows, rs, len, v, st); return true;
-  }
-  return false;
+  return rtb_dispatch(nob, [&]<int NOB, class TV, int PF>(RtbShape<NOB, TV, PF>) {
+    const unsigned gx = rt_grid_x(len, sizeof(TV), 1, vec_ok);
+    for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
+      hipLaunchKernelGGL((k_ptrb<NOB, TV, PF>), dim3(gx, ny), dim3(256), 0, st, tab, r0, rs, len,
+                         vec_ok ? 1 : 0);
+    });
+  });
 }
 
 void launch_ptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
                     bool vec_ok, hipStream_t st) {
-  const int v = vec_ok ? 1 : 0;
-  switch (nob) {  // the column widths of launch_matvec_rt
-    case 1: run_ptrt<1, 1, u32x4>(tab, nrows, rs, len, v, st); break;
-    case 2: run_ptrt<2, 1, u32x4>(tab, nrows, rs, len, v, st); break;
-    case 3: run_ptrt<3, 1, u32x4>(tab, nrows, rs, len, v, st); break;
-    case 4: run_ptrt<4, 1, u32x4>(tab, nrows, rs, len, v, st); break;
-    case 5: run_ptrt<5, 1, u32x4>(tab, nrows, rs, len, v, st); break;
-    case 6: run_ptrt<6, 1, u32x4>(tab, nrows, rs, len, v, st); break;
-    case 7: run_ptrt<7, 1, u32x2>(tab, nrows, rs, len, v, st); break;
-    case 8: run_ptrt<8, 1, u32x2>(tab, nrows, rs, len, v, st); break;
-    case 12: run_ptrt<12, 1, u32x2>(tab, nrows, rs, len, v, st); break;
-    case 16: run_ptrt<16, 1, uint32_t>(tab, nrows, rs, len, v, st); break;
-    case 24: run_ptrt<24, 1, uint32_t>(tab, nrows, rs, len, v, st); break;
-    default: run_ptrt<32, 1, uint32_t>(tab, nrows, rs, len, v, st); break;
-  }
+  rt_dispatch(nob, [&]<int NOB, int U, class TV>(RtShape<NOB, U, TV>) {
+    const unsigned gx = rt_grid_x(len, sizeof(TV), U, vec_ok);
+    for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
+      hipLaunchKernelGGL((k_ptrt<NOB, U, TV>), dim3(gx, ny), dim3(256), 0, st, tab, r0, rs, len,
+                         vec_ok ? 1 : 0);
+    });
+  });
 }
 
 }  // namespace cec

@@ -336,6 +336,98 @@ def test_wide_some_batch(torch, cess, corc, ln, mode):
         assert (enc.stat(_lib.CEC_STAT_FFTDEC_D_SEGMENTS) > 0) == (mode == 2)
 
 
+# ---- the table kernels against the in-layout kernels, bucket by bucket ---------------------------
+
+# (CEC_OPT_RT_MODE, lost fragments): mode 1 runs the per-bit mask product (k_rt / k_ptrt) in every
+# output bucket 1..8, 12, 16, 24, 32; mode 3 the bit-plane product (k_rtb / k_ptrb) in its four
+BUCKET_CASES = ([(1, c) for c in (1, 2, 3, 4, 5, 6, 7, 8, 9, 13, 17, 25)] +
+                [(3, c) for c in (1, 2, 3, 4)])
+# (shard length, view offset): 4117 = vector blocks and a tail that is not empty for 16-, 8- and
+# 4-byte columns (separate aligned buffers; the batch layout's shard stride is the odd length
+# itself, so there the same bytes come from the byte path); 333 bytes one byte into every
+# allocation = the byte path everywhere
+BUCKET_SHAPES = [(4117, 0), (333, 1)]
+
+
+def guarded_batch(torch, host, off):
+    """`host` ([nseg][shards][len]) on the device between two guard bands, `off` more bytes into
+    its allocation; returns (the whole allocation, the view)."""
+    flat = np.full(host.size + 2 * GUARD + off, 0xA5, dtype=np.uint8)
+    flat[GUARD + off:GUARD + off + host.size] = host.reshape(-1)
+    big = torch.from_numpy(flat).cuda()
+    return big, big[GUARD + off:GUARD + off + host.size].view(*host.shape)
+
+
+def batch_result(big, host, off):
+    """The batch back on the host after its guard bands were checked."""
+    got = big.cpu().numpy()
+    lo = GUARD + off
+    assert (got[:lo] == 0xA5).all() and (got[lo + host.size:] == 0xA5).all(), "guard band written"
+    return got[lo:lo + host.size].reshape(host.shape)
+
+
+@pytest.mark.parametrize("ln,off", BUCKET_SHAPES)
+@pytest.mark.parametrize("mode,nlost", BUCKET_CASES)
+def test_table_and_layout_kernels_agree(torch, cess, corc, mode, nlost, ln, off):
+    """RS(32,32) without the FFT-domain decoders, three segments with a different lost set each,
+    every lost shard rebuilt three ways: one per-segment ReconstructSomeBatch (the in-layout
+    kernel, a chunk per workgroup row), one uniform ReconstructBatch on segment 0's pattern (the
+    in-layout kernel, one chunk for the launch) and ReconstructDevice on separate buffers (the
+    table kernel). All agree with the C oracle bit for bit; nothing else is written."""
+    from cess_amd import _lib
+    k = m = 32
+    n, nseg = k + m, 3
+    rng = np.random.default_rng(70000 + 1000 * mode + 10 * nlost + off)
+    full = codewords(corc, k, m, ln, nseg)
+    enc = cess.New(k, m)
+    enc.set_option(_lib.CEC_OPT_FFTDEC_MIN, 0)
+    enc.set_option(_lib.CEC_OPT_RT_MODE, mode)
+    patterns = [random_pattern(rng, n, nlost) for _ in range(nseg)]
+
+    def batch_host(pats):
+        """Survivors from the codewords, garbage in every other shard."""
+        host = rng.integers(0, 256, (nseg, n, ln), dtype=np.uint8)
+        for s, (present, _) in enumerate(pats):
+            for i in survivors(cess, k, m, present):
+                host[s, i] = full[s][i]
+        return host
+
+    def run_batch(pats, call):
+        host = batch_host(pats)
+        dbig, d_data = guarded_batch(torch, host[:, :k].copy(), off)
+        pbig, d_par = guarded_batch(torch, host[:, k:].copy(), off)
+        call(d_data, d_par)
+        torch.cuda.synchronize()
+        got = np.concatenate([batch_result(dbig, host[:, :k], off),
+                              batch_result(pbig, host[:, k:], off)], axis=1)
+        for s, (_, lost) in enumerate(pats):
+            for i in range(n):
+                want = full[s][i] if i in lost else host[s, i]
+                assert np.array_equal(got[s, i], want), (s, i, "lost" if i in lost else "kept")
+        return got
+
+    presents = np.stack([p for p, _ in patterns])
+    per_seg = run_batch(patterns, lambda d, p: enc.ReconstructSomeBatch(
+        d, p, nseg, ln, presents, 1 - presents))
+    uniform = run_batch([patterns[0]] * nseg, lambda d, p: enc.ReconstructBatch(
+        d, p, nseg, ln, patterns[0][0]))
+
+    for s, (present, lost) in enumerate(patterns):
+        sg = Scattered(torch, cess, rng, k, m, full[s], present, lost, off=off)
+        before = {i: t.cpu().numpy() for i, t in enumerate(sg.src) if t is not None}
+        shards = list(sg.src)
+        enc.ReconstructDevice(shards, out={i: sg.dst[i] for i in lost})
+        torch.cuda.synchronize()
+        sg.check(("table", mode, nlost, ln, s))
+        for i, b in before.items():
+            assert np.array_equal(sg.src[i].cpu().numpy(), b), (s, i, "a source was written")
+        for i in lost:
+            table = sg.dst[i].cpu().numpy()
+            assert np.array_equal(table, per_seg[s, i]), (s, i, "table != per-segment")
+            if s == 0:
+                assert np.array_equal(table, uniform[0, i]), (i, "table != uniform")
+
+
 # ---- past kRtMaxOut outputs, and the widest geometry ---------------------------------------------
 
 
