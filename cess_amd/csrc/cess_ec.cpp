@@ -1408,8 +1408,12 @@ int cec_decode_rows(int k, int m, const uint8_t* present, const uint8_t* require
 // launch; the table is built on the host from the caller's arrays (which are not read after the
 // return), uploaded to a pool block on the codec's stream and complete before the launches, and
 // retired in stream order behind them.
+// With `d_ok` (cec_verify_ptrs) `dst` names expectations: the same programs and rows, run by the
+// compare forms of the kernels, which read what dst names and write only d_ok (preset to 1 here,
+// behind the validation). Their rows also hold the segment index, see launch_vptrs_*.
 static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_t* const* dst,
-                                 size_t nseg, size_t shard_len, hipStream_t st) {
+                                 size_t nseg, size_t shard_len, hipStream_t st,
+                                 uint8_t* d_ok = nullptr) {
   const int n = c->k + c->m, k = c->k;
   struct Group {
     ProgPtr prog;
@@ -1424,6 +1428,8 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
     const uint8_t* const* sp = src + s * n;
     uint8_t* const* dp = dst + s * n;
     for (int i = 0; i < n; ++i) {
+      if (d_ok && sp[i] && dp[i])
+        return set_err(CEC_EINVAL, "a shard is both a source and an expectation");
       key[i] = sp[i] ? 1 : 0;
       key[n + i] = !sp[i] && dp[i] ? 1 : 0;
     }
@@ -1442,6 +1448,7 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
     for (int o = 0; o < p.nout; ++o) {
       const uint8_t* d = dp[p.out_idx[o]];
       bits |= (uintptr_t)d;
+      if (d_ok) continue;  // a compare only reads: aliases are harmless
       for (int j = 0; j < k; ++j)
         if (d == sp[p.in_idx[j]])
           return set_err(CEC_EINVAL, "a destination is a survivor of its own segment");
@@ -1465,6 +1472,20 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
     launches.push_back({kind, nob, rs, {}});
     return launches.back();
   };
+  // one launch's kernel: the store forms (rebuild, encode) or the compare forms (verify)
+  auto launch_store = [&](const Launch& l, const uint64_t* tab, uint32_t nrows) {
+    if (l.kind == 0)
+      cec::launch_ptrs_rs21(tab, nrows, shard_len, vec_ok, st);
+    else if (l.kind != 1 || !cec::launch_ptrs_rtb(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st))
+      cec::launch_ptrs_rt(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st);
+  };
+  auto launch_compare = [&](const Launch& l, const uint64_t* tab, uint32_t nrows) {
+    if (l.kind == 0)
+      cec::launch_vptrs_rs21(tab, nrows, shard_len, vec_ok, d_ok, st);
+    else if (l.kind != 1 ||
+             !cec::launch_vptrs_rtb(tab, nrows, l.rs, l.nob, shard_len, vec_ok, d_ok, st))
+      cec::launch_vptrs_rt(tab, nrows, l.rs, l.nob, shard_len, vec_ok, d_ok, st);
+  };
   const bool ct21 = k == 2 && c->m == 1 && !c->force_generic;
   for (const Group& g : groups) {
     const Program& p = *g.prog;
@@ -1475,18 +1496,20 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
         l.rows.push_back((uint64_t)(uintptr_t)src[(size_t)s * n + p.in_idx[0]]);
         l.rows.push_back((uint64_t)(uintptr_t)src[(size_t)s * n + p.in_idx[1]]);
         l.rows.push_back((uint64_t)(uintptr_t)dst[(size_t)s * n + p.out_idx[0]]);
-        l.rows.push_back((uint64_t)p.out_idx[0]);
+        l.rows.push_back((uint64_t)p.out_idx[0] | (d_ok ? (uint64_t)s << 32 : 0));
       }
       continue;
     }
     int o0 = 0;
     for (const RtChunk& ch : p.chunks) {
       const bool rtb = cec::rt_takes_rtb(c->opts, ch.nob, ch.nin);  // as launch_chunk
-      Launch& l = launch_of(rtb && ch.nob <= 4 ? 1 : 2, ch.nob, (uint32_t)(1 + ch.nin + ch.nob));
+      Launch& l = launch_of(rtb && ch.nob <= 4 ? 1 : 2, ch.nob,
+                            (uint32_t)(1 + ch.nin + ch.nob + (d_ok ? 1 : 0)));
       for (uint32_t s : g.segs) {
         const size_t r0 = l.rows.size();
         l.rows.resize(r0 + l.rs, 0);
         uint64_t* r = l.rows.data() + r0;
+        if (d_ok) r[l.rs - 1] = s;
         r[0] = (uint64_t)(uintptr_t)ch.dev;
         for (int j = 0; j < ch.nin; ++j) r[1 + j] = (uint64_t)(uintptr_t)src[(size_t)s * n + p.in_idx[j]];
         for (int o = 0; o < ch.nout; ++o)
@@ -1513,13 +1536,15 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
       return set_err(CEC_EHIP, std::string("table upload: ") + hipGetErrorString(e));
     }
     up.arena.reset();
+    if (d_ok && (e = hipMemsetAsync(d_ok, 1, nseg, st)) != hipSuccess) {
+      c->pool.retire(d, bytes);
+      return set_err(CEC_EHIP, std::string("verify: ") + hipGetErrorString(e));
+    }
     const uint64_t* tab = static_cast<const uint64_t*>(d);
     for (const auto& l : launches) {
       const uint32_t nrows = (uint32_t)(l.rows.size() / l.rs);
-      if (l.kind == 0)
-        cec::launch_ptrs_rs21(tab, nrows, shard_len, vec_ok, st);
-      else if (l.kind != 1 || !cec::launch_ptrs_rtb(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st))
-        cec::launch_ptrs_rt(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st);
+      if (d_ok) launch_compare(l, tab, nrows);
+      else launch_store(l, tab, nrows);
       rc = check_launch();
       if (rc) break;
       tab += l.rows.size();
@@ -1527,6 +1552,9 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
     const int mrc = c->pool.mark(st);  // the table and the programs stay until these complete
     c->pool.retire(d, bytes);
     if (!rc) rc = mrc;
+  } else if (d_ok) {  // no segment has an expectation: every flag is 1
+    const hipError_t e = hipMemsetAsync(d_ok, 1, nseg, st);
+    if (e != hipSuccess) rc = set_err(CEC_EHIP, std::string("verify: ") + hipGetErrorString(e));
   }
   evict_decode(c);
   return rc;
@@ -1559,6 +1587,17 @@ int cec_encode_ptrs(cec_codec* c, const uint8_t* const* d_data_ptrs, uint8_t* co
   HIP_TRY(hipSetDevice(c->device));
   return reconstruct_ptrs_impl(c, src.data(), dst.data(), nseg, shard_len,
                                pick_stream(c, hip_stream));
+}
+
+int cec_verify_ptrs(cec_codec* c, const uint8_t* const* src, const uint8_t* const* expect,
+                    size_t nseg, size_t shard_len, uint8_t* d_ok, void* hip_stream) {
+  if (!c || (nseg && (!src || !expect || !d_ok))) return set_err(CEC_EINVAL, "null");
+  if (int rc = check_batch(nseg, shard_len)) return rc;
+  if (nseg == 0) return CEC_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  // the expectations sit where a rebuild's destinations do; the compare kernels only read them
+  return reconstruct_ptrs_impl(c, src, const_cast<uint8_t* const*>(expect), nseg, shard_len,
+                               pick_stream(c, hip_stream), d_ok);
 }
 
 int cec_reconstruct_partial_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size_t nseg,

@@ -147,6 +147,18 @@ bool launch_ptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, 
                      bool vec_ok, hipStream_t st);
 void launch_ptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
                     bool vec_ok, hipStream_t st);
+// The compare forms of the three (cec_verify_ptrs): the addresses in the output positions name
+// the expected bytes, which are read and compared with the product instead of written; ok[segment]
+// (device, preset to 1 by the caller) = 0 for a row that differs, and nothing else is written.
+// Rows carry their segment: RS(2,1) row = {input 0, input 1, expected, case | segment << 32};
+// run-time row = {program chunk, nin inputs, nout expected, ..., segment}, the segment in word
+// rs - 1 (rs >= 2 + nin + nout).
+void launch_vptrs_rs21(const uint64_t* tab, uint32_t nrows, uint64_t len, bool vec_ok, uint8_t* ok,
+                       hipStream_t st);
+bool launch_vptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
+                      bool vec_ok, uint8_t* ok, hipStream_t st);
+void launch_vptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
+                     bool vec_ok, uint8_t* ok, hipStream_t st);
 
 // SHA-256 of `n` equal-length buffers, written as 64 lowercase hex characters each into
 // `hex_out` (device, n * 64 bytes). If `ptrs` is null, buffer i is shard (i % nshards) of

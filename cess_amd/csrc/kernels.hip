@@ -788,6 +788,44 @@ __device__ __forceinline__ void stv(uint8_t* p, TV v) { st16<NT, TV>(p, v); }
 template <bool NT, class TV>
 __device__ __forceinline__ void stv(gu8* p, TV v) { gst<NT, TV>(p, v); }
 
+// What the run-time products and the RS(2,1) table tile do with a finished column, next to where
+// they find it (the addressing policies below). col() takes a column of TV at p, flush() ends a
+// lane's columns, and on the byte paths `at(p) = y` takes the byte y at p: an assignment, so that
+// value and address are evaluated in the order of the plain store it stands for.
+// StoreSink writes the column: the rebuild and the encode.
+struct StoreSink {
+  template <bool NT, class TV, class Ptr>
+  __device__ __forceinline__ void col(Ptr p, TV y) { stv<NT, TV>(p, y); }
+  template <class Ptr>
+  __device__ __forceinline__ auto& at(Ptr p) { return *p; }
+  __device__ __forceinline__ void flush() {}
+};
+// CmpSink (cec_verify_ptrs) reads the expected column at p with the load flavour of the inputs
+// and ORs its XOR with the product into `bad`; nothing at p is written. flush() clears the
+// segment's flag when a bit differed: a plain byte store of 0 behind a branch, off the columns'
+// straight line, and every lane that saw a difference stores the same value (as k_verify21).
+__device__ __forceinline__ uint32_t any_bits(uint32_t z) { return z; }
+__device__ __forceinline__ uint32_t any_bits(u32x2 z) { return z.x | z.y; }
+__device__ __forceinline__ uint32_t any_bits(u32x4 z) { return z.x | z.y | z.z | z.w; }
+struct CmpSink {
+  gu8* ok;  // the segment's byte of d_ok
+  uint32_t bad = 0;
+  template <bool NT, class TV, class Ptr>
+  __device__ __forceinline__ void col(Ptr p, TV y) { bad |= any_bits(ldv<NT, TV>(p) ^ y); }
+  template <class Ptr>
+  struct Byte {
+    CmpSink& s;
+    Ptr p;
+    __device__ __forceinline__ void operator=(uint8_t y) { s.bad |= (uint8_t)(*p ^ y); }
+  };
+  template <class Ptr>
+  __device__ __forceinline__ Byte<Ptr> at(Ptr p) { return {*this, p}; }
+  __device__ __forceinline__ void flush() {
+    if (bad) *ok = 0;
+    bad = 0;
+  }
+};
+
 // Where a workgroup row of the run-time products finds its program chunk P and its shards: key(j)
 // names input j of the program, in(key) / out(o) give a shard's address. The index type of key
 // is the caller's: the address arithmetic of the two products differs in it (32-bit in rt_body,
@@ -892,8 +930,8 @@ __device__ __forceinline__ uint8_t* shard_ptr_sel(const Layout& L, uint32_t idx,
 
 // The per-bit mask product of one workgroup over program chunk P: any output count up to the
 // bucket NOB, U columns of TV per lane.
-template <int NOB, int U, class TV, class Addr>
-__device__ __forceinline__ void rt_body(typename Addr::Arg a, int vec_ok) {
+template <int NOB, int U, class TV, class Addr, class Sink = StoreSink>
+__device__ __forceinline__ void rt_body(typename Addr::Arg a, int vec_ok, Sink sink = Sink{}) {
   const cu32* __restrict__ P = a.P;
   const uint32_t nout = P[1];
   const uint64_t len = a.len();
@@ -919,10 +957,11 @@ __device__ __forceinline__ void rt_body(typename Addr::Arg a, int vec_ok) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const uint64_t v = base + u * 256;
-          if (v < nvec) stv<false, TV>(dst + v * VB, acc[o][u]);
+          if (v < nvec) sink.template col<false, TV>(dst + v * VB, acc[o][u]);
         }
       }
     }
+    sink.flush();
     if (!(len % VB) || blockIdx.x != gridDim.x - 1) return;
   }
   // byte path: whole shard (vec_ok == 0, grid covers len) or the tail (last block)
@@ -936,7 +975,8 @@ __device__ __forceinline__ void rt_body(typename Addr::Arg a, int vec_ok) {
   rt_accumulate<NOB, 1, uint32_t>(acc, P, a, ld);
 #pragma unroll
   for (int o = 0; o < NOB; ++o)
-    if (o < (int)nout) a.out(o)[i] = (uint8_t)acc[o][0];
+    if (o < (int)nout) sink.at(a.out(o) + i) = (uint8_t)acc[o][0];
+  sink.flush();
 }
 
 // Bit-plane run-time matvec for few outputs (k_rtb): per output o and coefficient bit b one
@@ -946,8 +986,8 @@ __device__ __forceinline__ void rt_body(typename Addr::Arg a, int vec_ok) {
 // stream through (the next column's load is issued before the current one is folded in), so the
 // registers are the 8 * NOB accumulators: decode of a few lost fragments of a wide code (the
 // restoral case) and partial rebuilds, where nout << nin.
-template <int NOB, class TV, int PF, class Addr>
-__device__ __forceinline__ void rtb_body(typename Addr::Arg a, int vec_ok) {
+template <int NOB, class TV, int PF, class Addr, class Sink = StoreSink>
+__device__ __forceinline__ void rtb_body(typename Addr::Arg a, int vec_ok, Sink sink = Sink{}) {
   const cu32* __restrict__ P = a.P;
   const uint32_t nin = P[0], nout = P[1];
   const uint64_t len = a.len();
@@ -993,7 +1033,8 @@ __device__ __forceinline__ void rtb_body(typename Addr::Arg a, int vec_ok) {
       fold(t, [&](uint32_t key) CEC_AI { return ldv<true, TV>(a.in(key) + v * VB); });
 #pragma unroll
       for (int o = 0; o < NOB; ++o)
-        if (o < (int)nout) stv<true, TV>(a.out(o) + v * VB, horner(t[o]));
+        if (o < (int)nout) sink.template col<true, TV>(a.out(o) + v * VB, horner(t[o]));
+      sink.flush();
     }
     if (!(len % VB) || blockIdx.x != gridDim.x - 1) return;
   }
@@ -1009,7 +1050,8 @@ __device__ __forceinline__ void rtb_body(typename Addr::Arg a, int vec_ok) {
   fold(t, [&](uint32_t key) CEC_AI -> uint32_t { return a.in(key)[i]; });
 #pragma unroll
   for (int o = 0; o < NOB; ++o)
-    if (o < (int)nout) a.out(o)[i] = (uint8_t)horner(t[o]);
+    if (o < (int)nout) sink.at(a.out(o) + i) = (uint8_t)horner(t[o]);
+  sink.flush();
 }
 
 // The in-layout entry points (the pointer-table ones, k_ptrt and k_ptrb, are further down).
@@ -1780,8 +1822,9 @@ void launch_fill_splitmix(uint8_t* out, uint64_t seg_bytes, uint64_t nseg, uint6
 // the closed-form rebuild of data fragment 0 / 1 (inputs: the other data fragment, the parity),
 // 2 = the encode (inputs: d0, d1). One launch mixes the cases as k_ct_dec1_mixed21 does (a
 // wave-uniform branch); segments with nothing wanted have no row.
-template <class P, bool NT>
-__device__ __forceinline__ void ptr_tile21(gu8* i0, gu8* i1, gu8* o0, uint64_t len, int vec_ok) {
+template <class P, bool NT, class Sink = StoreSink>
+__device__ __forceinline__ void ptr_tile21(gu8* i0, gu8* i1, gu8* o0, uint64_t len, int vec_ok,
+                                           Sink sink = Sink{}) {
   using TV = u32x4;
   constexpr int VB = sizeof(TV);
   if (vec_ok) {
@@ -1792,10 +1835,11 @@ __device__ __forceinline__ void ptr_tile21(gu8* i0, gu8* i1, gu8* o0, uint64_t l
         if constexpr (decltype(J)::value == 0) return gld<NT, TV>(i0 + off);
         else return gld<NT, TV>(i1 + off);
       };
-      auto st = [&](auto, TV y) CEC_AI { gst<NT, TV>(o0 + off, y); };
+      auto st = [&](auto, TV y) CEC_AI { sink.template col<NT, TV>(o0 + off, y); };
       if constexpr (Rs21Closed<P>::missing >= 0) ct_column_rs21<Rs21Closed<P>::missing, TV>(ld, st);
       else if constexpr (use_horner<P>(1)) ct_column_horner<P, TV>(ld, st);
       else ct_column_stream<P, 1, TV>(ld, st);
+      sink.flush();
     }
     if (!(len % VB) || blockIdx.x != gridDim.x - 1) return;
   }
@@ -1807,9 +1851,10 @@ __device__ __forceinline__ void ptr_tile21(gu8* i0, gu8* i1, gu8* o0, uint64_t l
     if constexpr (decltype(J)::value == 0) return i0[i];
     else return i1[i];
   };
-  auto st = [&](auto, uint32_t y) CEC_AI { o0[i] = (uint8_t)y; };
+  auto st = [&](auto, uint32_t y) CEC_AI { sink.at(o0 + i) = (uint8_t)y; };
   if constexpr (use_horner<P>(1)) ct_column_horner<P, uint32_t>(ld, st);
   else ct_column_stream<P, 1, uint32_t>(ld, st);
+  sink.flush();
 }
 
 template <bool NT>
@@ -1868,6 +1913,80 @@ void launch_ptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, u
     for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
       hipLaunchKernelGGL((k_ptrt<NOB, U, TV>), dim3(gx, ny), dim3(256), 0, st, tab, r0, rs, len,
                          vec_ok ? 1 : 0);
+    });
+  });
+}
+
+// The compare forms (cec_verify_ptrs): the same tile and products with CmpSink, so the addresses
+// in the output positions of a row are read, not written, and the only store of a launch is the
+// 0 into ok[segment] of a row that differs (ok preset to 1 by the caller). The rows say which
+// segment they belong to (several rows of one segment, one per program chunk, share a flag):
+// RS(2,1) in the high half of the case word, {input 0, input 1, expected, case | segment << 32};
+// the run-time rows in one more word at their end, {program chunk, nin inputs, nout expected,
+// (padding up to rs - 1,) segment}, which leaves TableAddr's view of the row as it is.
+__device__ __forceinline__ CmpSink cmp_sink(uint8_t* ok, uint64_t seg) {
+  return CmpSink{gptr((uint64_t)(uintptr_t)ok) + seg};
+}
+
+template <bool NT>
+__global__ __launch_bounds__(256) void k_ptr21v(const uint64_t* __restrict__ tab, uint32_t row0,
+                                                uint64_t len, int vec_ok, uint8_t* ok) {
+  const cu64* __restrict__ row = tab_row(tab, row0 + blockIdx.y, 4);
+  gu8* const i0 = gptr(row[0]);
+  gu8* const i1 = gptr(row[1]);
+  gu8* const x0 = gptr(row[2]);
+  const uint32_t e = (uint32_t)row[3];
+  const CmpSink sink = cmp_sink(ok, row[3] >> 32);
+  if (e == 0) ptr_tile21<Dec1CT<2, 1, 0>, NT>(i0, i1, x0, len, vec_ok, sink);
+  else if (e == 1) ptr_tile21<Dec1CT<2, 1, 1>, NT>(i0, i1, x0, len, vec_ok, sink);
+  else if (e == 2) ptr_tile21<EncCT<2, 1>, NT>(i0, i1, x0, len, vec_ok, sink);
+}
+
+template <int NOB, int U, class TV>
+__global__ __launch_bounds__(256) void k_ptrtv(const uint64_t* __restrict__ tab, uint32_t row0,
+                                               uint32_t rs, uint64_t len, int vec_ok,
+                                               uint8_t* ok) {
+  const uint64_t r = row0 + blockIdx.y;
+  rt_body<NOB, U, TV, TableAddr>(TableAddr(tab, r, rs, len), vec_ok,
+                                 cmp_sink(ok, tab_row(tab, r, rs)[rs - 1]));
+}
+
+template <int NOB, class TV, int PF>
+__global__ __launch_bounds__(256) void k_ptrbv(const uint64_t* __restrict__ tab, uint32_t row0,
+                                               uint32_t rs, uint64_t len, int vec_ok,
+                                               uint8_t* ok) {
+  const uint64_t r = row0 + blockIdx.y;
+  rtb_body<NOB, TV, PF, TableAddr>(TableAddr(tab, r, rs, len), vec_ok,
+                                   cmp_sink(ok, tab_row(tab, r, rs)[rs - 1]));
+}
+
+void launch_vptrs_rs21(const uint64_t* tab, uint32_t nrows, uint64_t len, bool vec_ok, uint8_t* ok,
+                       hipStream_t st) {
+  const unsigned gx = rt_grid_x(len, 16, 1, vec_ok);
+  for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
+    hipLaunchKernelGGL((k_ptr21v<true>), dim3(gx, ny), dim3(256), 0, st, tab, r0, len,
+                       vec_ok ? 1 : 0, ok);
+  });
+}
+
+bool launch_vptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
+                      bool vec_ok, uint8_t* ok, hipStream_t st) {
+  return rtb_dispatch(nob, [&]<int NOB, class TV, int PF>(RtbShape<NOB, TV, PF>) {
+    const unsigned gx = rt_grid_x(len, sizeof(TV), 1, vec_ok);
+    for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
+      hipLaunchKernelGGL((k_ptrbv<NOB, TV, PF>), dim3(gx, ny), dim3(256), 0, st, tab, r0, rs, len,
+                         vec_ok ? 1 : 0, ok);
+    });
+  });
+}
+
+void launch_vptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
+                     bool vec_ok, uint8_t* ok, hipStream_t st) {
+  rt_dispatch(nob, [&]<int NOB, int U, class TV>(RtShape<NOB, U, TV>) {
+    const unsigned gx = rt_grid_x(len, sizeof(TV), U, vec_ok);
+    for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
+      hipLaunchKernelGGL((k_ptrtv<NOB, U, TV>), dim3(gx, ny), dim3(256), 0, st, tab, r0, rs, len,
+                         vec_ok ? 1 : 0, ok);
     });
   });
 }

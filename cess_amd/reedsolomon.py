@@ -97,6 +97,9 @@ def check(rc: int, what: str = "") -> None:
     raise e
 
 
+_check_rc = check  # for methods with a parameter named `check`
+
+
 def _as_u8(buf) -> np.ndarray:
     if isinstance(buf, np.ndarray):
         if buf.dtype != np.uint8 or not buf.flags.c_contiguous:
@@ -386,6 +389,82 @@ class Encoder:
                                              self._device_stream(stream)), "ReconstructDevice")
         for i, t in outs.items():
             shards[i] = t
+
+    def VerifyDevice(self, shards: Sequence, stream=None) -> bool:
+        """klauspost Verify on one segment whose k + m shards are separate 1-D uint8 device
+        tensors: True when the m parity tensors equal the encode of the k data tensors. Nothing is
+        written or copied (cec_verify_ptrs). Enqueued on `stream` (default: torch's current
+        stream, or a raw integer handle, 0 = the null stream), which is then synchronised to
+        read the flag. The flag's byte is allocated on that stream too."""
+        import torch
+        if len(shards) != self.Shards:
+            raise ErrTooFewShards(ErrTooFewShards.__doc__)
+        if any(s is None for s in shards):
+            raise ErrShardNoData(ErrShardNoData.__doc__)
+        self._check_device_shards(shards)
+        if self.ParityShards == 0:
+            return True
+        dev = torch.device("cuda", self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        elif isinstance(stream, int):
+            stream = (torch.cuda.ExternalStream(stream, device=dev) if stream
+                      else torch.cuda.default_stream(dev))
+        with torch.cuda.stream(stream):  # the allocator hands out a block of that stream
+            d_ok = torch.empty(1, dtype=torch.uint8, device=dev)
+        self.VerifyDeviceBatch([list(shards)], d_ok=d_ok, stream=stream)
+        # the copy below runs on torch's current stream, which nothing orders behind `stream`
+        stream.synchronize()
+        return bool(d_ok.cpu()[0])
+
+    def VerifyDeviceBatch(self, segments: Sequence, check=None, d_ok=None, stream=None):
+        """Verify many segments held as lists of k + m 1-D uint8 device tensors (None = absent)
+        in place (cec_verify_ptrs). `check` is None, or per segment either None or k + m flags
+        naming the present shards to treat as expectations: each is recomputed from the
+        segment's other present shards and compared, so any held shard can be checked while
+        others are missing. None for a segment: every present parity shard is an expectation and
+        the present data shards are the sources. Returns the uint8 device tensor of
+        len(segments) flags (1 = every expectation matched, or there was none), `d_ok` if given.
+        Every tensor, `d_ok` included, must be contiguous and on the codec's GPU (TypeError for a
+        shard, ErrInvalidInput for `d_ok`). Enqueued on `stream` (default: torch's current
+        stream) and not waited for: read the flags on that stream, or synchronise it first."""
+        import torch
+        nseg, n, k = len(segments), self.Shards, self.DataShards
+        if check is not None and len(check) != nseg:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        dev = torch.device("cuda", self.device)
+        if d_ok is None:
+            d_ok = torch.empty(nseg, dtype=torch.uint8, device=dev)
+        elif (d_ok.dtype != torch.uint8 or d_ok.dim() != 1 or d_ok.numel() != nseg
+              or d_ok.device != dev or not d_ok.is_contiguous()):
+            # the library writes nseg consecutive bytes at its address on the codec's GPU
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        if nseg == 0:
+            return d_ok
+        if self.ParityShards == 0:
+            return d_ok.fill_(1)
+        src = (c_void_p * (nseg * n))()
+        exp = (c_void_p * (nseg * n))()
+        held = []
+        for s, shards in enumerate(segments):
+            if len(shards) != n:
+                raise ErrTooFewShards(ErrTooFewShards.__doc__)
+            flags = check[s] if check is not None else None
+            if flags is None:
+                flags = [False] * k + [True] * self.ParityShards
+            elif len(flags) != n:
+                raise ErrInvalidInput(ErrInvalidInput.__doc__)
+            for i, t in enumerate(shards):
+                if t is None:
+                    continue
+                if t.device != dev:  # (_dev_ptr below refuses host and strided tensors)
+                    raise TypeError("device shards must live on the codec's GPU")
+                held.append(t)
+                (exp if flags[i] else src)[s * n + i] = _dev_ptr(t)
+        size = self._check_device_shards(held)
+        _check_rc(self._lib.cec_verify_ptrs(self._h, src, exp, nseg, size, _dev_ptr(d_ok),
+                                            self._device_stream(stream)), "VerifyDeviceBatch")
+        return d_ok
 
     def _check_device_shards(self, tensors) -> int:
         import torch

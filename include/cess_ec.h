@@ -91,9 +91,9 @@ int cec_verify(cec_codec* codec, uint8_t* const* shards, size_t shard_len, int* 
  * cec_reconstruct_batch of RS(2,1) with one pattern (per_segment = 0). Every other rebuild reads
  * a decode program from the codec's cache, which may evict it while a graph still points at it:
  * do not capture those, nor cec_reconstruct_some_batch, nor the pointer-table calls
- * (cec_reconstruct_ptrs, cec_encode_ptrs: their kernels read a codec-owned table that is retired
- * once the call's launches complete). A single 16 MiB RS(2,1) segment's encode + three rebuilds:
- * 29.5 us eagerly, 24.8 us as one graph (profiles/r05/graph_probe.log). */
+ * (cec_reconstruct_ptrs, cec_encode_ptrs, cec_verify_ptrs: their kernels read a codec-owned
+ * table that is retired once the call's launches complete). A single 16 MiB RS(2,1) segment's
+ * encode + three rebuilds: 29.5 us eagerly, 24.8 us as one graph (profiles/r05/graph_probe.log). */
 int cec_encode_batch(cec_codec* codec, const uint8_t* d_data, uint8_t* d_parity, size_t nseg,
                      size_t shard_len, void* hip_stream);
 /* Rebuild missing shards in place in the same layout. `present` is a host array of k+m flags
@@ -166,6 +166,39 @@ int cec_reconstruct_partial_batch(cec_codec* codec, uint8_t* d_data, uint8_t* d_
  * recomputed into codec-owned scratch and compared; nothing in the batch is written. */
 int cec_verify_batch(cec_codec* codec, const uint8_t* d_data, const uint8_t* d_parity,
                      size_t nseg, size_t shard_len, uint8_t* d_ok, void* hip_stream);
+/* Verify for scattered shards, in place and read-only. src, expect: HOST arrays of nseg*(k+m)
+ * DEVICE pointers laid out as in cec_reconstruct_ptrs; d_ok: device memory of nseg bytes.
+ * src[s*n+i] NULL = shard i of segment s is not a source. expect[s*n+i] non-NULL = recompute shard
+ * i of segment s from the segment's survivors and compare it with the shard_len bytes there.
+ * d_ok[s] = 1 when every expectation of segment s matched, or it had none; otherwise 0.
+ * klauspost's Verify is src = the k data shards, expect = the m parity shards; any missing shard
+ * may be the one checked, e.g. RS(4,2) with d1 lost: src = {d0, -, d2, d3, p0, -}, expect =
+ * {-, -, -, -, -, p1} checks p1 against the others without rebuilding d1.
+ *  - A shard is a source or an expectation, never both: src[s*n+i] and expect[s*n+i] both
+ *    non-NULL gives CEC_EINVAL (ignoring one would report bytes verified that nobody compared).
+ *  - Reads: only the k survivors cec_survivors names for the pattern of non-NULL src entries, and
+ *    the expected buffers. Other sources may hold anything.
+ *  - Writes: nothing but the nseg bytes of d_ok (preset to 1 on hip_stream ahead of the kernels,
+ *    which clear the flag of a segment that differs). No scratch parity, no batch-sized
+ *    allocation. A segment with no expectation gets no workgroup and d_ok[s] = 1.
+ *  - Validation: everything is validated before anything is enqueued; on an error d_ok is not
+ *    written. A NULL array, or a NULL d_ok, with nseg > 0: CEC_EINVAL. A segment with an
+ *    expectation and fewer than k sources: CEC_ETOOFEW. shard_len == 0: CEC_ESHARDLEN. nseg == 0:
+ *    CEC_OK. A segment with fewer than k sources and no expectation is no error, as a segment
+ *    with no destination in cec_reconstruct_ptrs: its shards are not counted, and d_ok[s] = 1.
+ *    Sources and expectations may alias, within and across segments: the call only reads them.
+ *  - Pointer arrays, alignment: as cec_reconstruct_ptrs. Both arrays belong to the caller again
+ *    on return; the work is enqueued on hip_stream and not waited for. Any alignment and any
+ *    shard_len >= 1 is correct; 16-byte (or 8-, 4-byte) columns with a byte tail when every
+ *    address read is 16-byte aligned, otherwise the whole call runs byte-wise.
+ *  - HIP graph capture: not capturable, for the reasons given at cec_reconstruct_ptrs (the
+ *    codec-owned table and, for every code but RS(2,1), the cached decode programs).
+ * Decode programs come from the codec's LRU cache under the keys of cec_reconstruct_ptrs with the
+ * expectation mask as the required mask: a verify and a rebuild of one pattern share an entry.
+ * The kernels are the compare forms of the table-addressed ones (same column bodies, the store
+ * replaced by a load and a compare); RS(32,32) takes the run-time kernels here too. */
+int cec_verify_ptrs(cec_codec* codec, const uint8_t* const* src, const uint8_t* const* expect,
+                    size_t nseg, size_t shard_len, uint8_t* d_ok, void* hip_stream);
 /* GF(2^8) addition of device buffers: d_dst[0..len) ^= d_src[j*src_stride ..][0..len) for
  * j < nsrc (src_stride >= len when nsrc > 1). Enqueued on hip_stream, which must belong to the
  * device holding the buffers (no codec: the caller's current device and stream decide). */

@@ -173,6 +173,9 @@ pub mod sys {
         pub fn cec_verify_batch(c: *mut cec_codec, d_data: *const u8, d_parity: *const u8,
                                 nseg: usize, shard_len: usize, d_ok: *mut u8,
                                 stream: *mut c_void) -> c_int;
+        pub fn cec_verify_ptrs(c: *mut cec_codec, src: *const *const u8,
+                               expect: *const *const u8, nseg: usize, shard_len: usize,
+                               d_ok: *mut u8, stream: *mut c_void) -> c_int;
         pub fn cec_xor_batch(d_dst: *mut u8, d_src: *const u8, nsrc: usize, src_stride: usize,
                              len: usize, stream: *mut c_void) -> c_int;
         pub fn cec_encode_idx_batch(c: *mut cec_codec, d_shard: *const u8,
@@ -541,6 +544,27 @@ impl ReedSolomon {
         }
         check(cec_reconstruct_ptrs(self.c, src.as_ptr(), dst.as_ptr(), src.len() / n, shard_len,
                                    stream))
+    }
+
+    /// Verify scattered device shards in place (`cec_verify_ptrs`): `src` and `expect` hold
+    /// `nseg * (k + m)` device addresses, segment by segment. A non-null `expect` entry is
+    /// recomputed from the segment's survivors among the non-null `src` entries and compared with
+    /// the bytes there; an entry set in both slices is refused. `d_ok` (device, `nseg` bytes)
+    /// receives 1 per segment whose expectations all matched (or that had none), else 0. Nothing
+    /// else is written. Enqueued on `stream` and not waited for; both slices may be reused as
+    /// soon as the call returns.
+    ///
+    /// # Safety
+    /// Every non-null address must be device memory of `shard_len` bytes (`d_ok`: `nseg` bytes) on
+    /// the codec's GPU that stays valid until the stream has passed the call's work.
+    pub unsafe fn verify_device(&self, src: &[*const u8], expect: &[*const u8], shard_len: usize,
+                                d_ok: *mut u8, stream: *mut c_void) -> Result<(), Error> {
+        let n = self.k + self.m;
+        if src.len() != expect.len() || src.len() % n != 0 {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        check(cec_verify_ptrs(self.c, src.as_ptr(), expect.as_ptr(), src.len() / n, shard_len,
+                              d_ok, stream))
     }
 
     /// The decode rows of the `required` lost shards of pattern `present` (`cec_decode_rows`):
