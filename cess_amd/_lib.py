@@ -79,6 +79,11 @@ SIGNATURES = {
     "cec_verify_ptrs": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_size_t,
                                 c_size_t, c_void_p, c_void_p]),
     "cec_xor_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "cec_reconstruct_partial_ptrs": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p),
+                                             POINTER(c_uint8), c_size_t, c_size_t, c_int,
+                                             c_void_p]),
+    "cec_xor_ptrs": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_size_t, c_size_t,
+                             c_size_t, c_void_p]),
     "cec_encode_idx_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_size_t,
                                      c_size_t, c_int, c_void_p]),
     "cec_update_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,

@@ -25,6 +25,7 @@
 #include <new>
 #include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/cess_ec.h"
@@ -594,8 +595,8 @@ void scratch_release(cec_codec* c, const Scratch& s, hipStream_t st) {
 }
 
 // Cache keys start with a kind tag, so keys of different kinds never compare equal whatever
-// their lengths: 'F' full rebuild, 'P' partial rebuild, 'R' rebuild of a required subset (decode
-// LRU); 'S' / 'Q' / 'T' the per-segment plans of cec_reconstruct_batch /
+// their lengths: 'F' full rebuild, 'P' partial rebuild, 'R' rebuild of a required subset, 'W'
+// partial rebuild of a wanted subset (decode LRU); 'S' / 'Q' / 'T' the per-segment plans of cec_reconstruct_batch /
 // cec_reconstruct_partial_batch / cec_reconstruct_some_batch.
 std::string pattern_key(const uint8_t* present, int n, bool data_only) {
   std::string key(n + 2, '\0');
@@ -605,10 +606,26 @@ std::string pattern_key(const uint8_t* present, int n, bool data_only) {
   return key;
 }
 
-std::string partial_key(const uint8_t* present, const uint8_t* held, int n, bool data_only) {
+// Key of a partial rebuild: kind 'P', the pattern, then the held flags. With `required` (n flags;
+// flags of present shards are ignored) only the lost shards it flags are outputs
+// (cec_reconstruct_partial_ptrs): kind 'W' and the wanted flags behind the held ones, unless the
+// subset names every lost shard, which is the 'P' entry of cec_reconstruct_partial_batch. `want`
+// (n flags, may be null without `required`) receives the normalised subset.
+std::string partial_key(const uint8_t* present, const uint8_t* held, int n, bool data_only,
+                        int k = 0, const uint8_t* required = nullptr, uint8_t* want = nullptr) {
   std::string key = pattern_key(present, n, data_only);
   key[0] = 'P';
   for (int i = 0; i < n; ++i) key.push_back(held[i] ? 1 : 0);
+  if (!required) return key;
+  bool all = true;
+  for (int i = 0; i < n; ++i) {
+    const bool lost = !present[i] && !(data_only && i >= k);
+    want[i] = lost && required[i] ? 1 : 0;
+    if (lost && !want[i]) all = false;
+  }
+  if (all) return key;
+  key[0] = 'W';
+  for (int i = 0; i < n; ++i) key.push_back((char)want[i]);
   return key;
 }
 
@@ -658,6 +675,21 @@ int solve_pattern(int k, int m, const BigMat& E, const uint8_t* flags, bool data
   return CEC_OK;
 }
 
+// Keep the rows of a solved plan whose outputs `want` flags (n flags), in their order.
+void keep_wanted_rows(BigPlan* plan, const uint8_t* want, int k) {
+  int w = 0;
+  for (int o = 0; o < plan->nout; ++o) {
+    if (!want[plan->out_idx[o]]) continue;
+    if (w != o) {
+      plan->out_idx[w] = plan->out_idx[o];
+      std::memcpy(plan->coef.v[w], plan->coef.v[o], k);
+    }
+    ++w;
+  }
+  plan->nout = w;
+  plan->coef.rows = w;
+}
+
 // Decode program for one erasure pattern (LRU-cached). With `required`, only the lost shards it
 // flags are outputs (rows of the same decode: the survivors read do not change). `key_out`
 // receives the pattern's cache key.
@@ -683,19 +715,7 @@ int get_decode(cec_codec* c, const uint8_t* present, bool data_only, ProgPtr* ou
   std::memcpy(flags, key.data() + 1, n);
   int rc = solve_pattern(c->k, c->m, *c->E, flags, data_only, sc);
   if (rc) return rc;
-  if (some) {  // keep the wanted rows
-    int w = 0;
-    for (int o = 0; o < plan->nout; ++o) {
-      if (!want[plan->out_idx[o]]) continue;
-      if (w != o) {
-        plan->out_idx[w] = plan->out_idx[o];
-        std::memcpy(plan->coef.v[w], plan->coef.v[o], c->k);
-      }
-      ++w;
-    }
-    plan->nout = w;
-    plan->coef.rows = w;
-  }
+  if (some) keep_wanted_rows(plan, want, c->k);
   ProgPtr prog;
   if (plan->nout > 0) {
     // RS(32,32) rebuilds of several shards: also the FFT-domain plan (picked at launch by the
@@ -729,10 +749,17 @@ int get_decode(cec_codec* c, const uint8_t* present, bool data_only, ProgPtr* ou
 // column with zero coefficients), so the outputs are still written (as zeros). Cached in the
 // decode LRU under its own key, which `key_out` receives.
 int get_partial(cec_codec* c, const uint8_t* present, const uint8_t* held, bool data_only,
-                ProgPtr* out, HostImages* keep = nullptr, std::string* key_out = nullptr) {
+                ProgPtr* out, HostImages* keep = nullptr, std::string* key_out = nullptr,
+                const uint8_t* required = nullptr) {
   const int n = c->k + c->m;
-  std::string key = partial_key(present, held, n, data_only);
+  uint8_t want[cec::kMaxShards];
+  std::string key = partial_key(present, held, n, data_only, c->k, required, want);
   if (key_out) *key_out = key;
+  const bool some = key[0] == 'W';
+  if (some && !std::memchr(want, 1, n)) {  // nothing asked for: nothing to do
+    *out = std::make_shared<const Program>();
+    return CEC_OK;
+  }
   if ((*out = cache_find(c, key))) return CEC_OK;
   auto& sc = c->plan_scratch();
   auto* plan = &sc.plan;
@@ -740,6 +767,7 @@ int get_partial(cec_codec* c, const uint8_t* present, const uint8_t* held, bool 
   std::memcpy(flags, key.data() + 1, n);
   int rc = solve_pattern(c->k, c->m, *c->E, flags, data_only, sc);
   if (rc) return rc;
+  if (some) keep_wanted_rows(plan, want, c->k);
   ProgPtr prog;
   if (plan->nout > 0) {
     uint8_t in_sub[cec::kMaxShards];
@@ -1408,9 +1436,93 @@ int cec_decode_rows(int k, int m, const uint8_t* present, const uint8_t* require
 // launch; the table is built on the host from the caller's arrays (which are not read after the
 // return), uploaded to a pool block on the codec's stream and complete before the launches, and
 // retired in stream order behind them.
-// With `d_ok` (cec_verify_ptrs) `dst` names expectations: the same programs and rows, run by the
-// compare forms of the kernels, which read what dst names and write only d_ok (preset to 1 here,
-// behind the validation). Their rows also hold the segment index, see launch_vptrs_*.
+
+// One kernel launch of such a call and its rows of the table.
+struct PtrLaunch {
+  int kind;  // 0: RS(2,1) compile-time, 1: bit-plane (k_rtb's cases), 2: general, 3: cec_xor_ptrs
+  int nob;
+  uint32_t rs;
+  std::vector<uint64_t> rows;
+};
+
+static PtrLaunch& ptr_launch_of(std::vector<PtrLaunch>& launches, int kind, int nob, uint32_t rs) {
+  for (auto& l : launches)
+    if (l.kind == kind && l.nob == nob && l.rs == rs) return l;
+  launches.push_back({kind, nob, rs, {}});
+  return launches.back();
+}
+
+// The run-time rows of program p for the segments `segs`: per chunk and segment one row {program
+// chunk, nin inputs, nout outputs} in the launch of the chunk's kernel and bucket, the addresses
+// taken from the segment's n entries of src and dst. With `seg_word` the rows are one word longer
+// and hold the segment index in their last word (the compare forms).
+static void add_rt_rows(const cec_codec* c, std::vector<PtrLaunch>& launches, const Program& p,
+                        const std::vector<uint32_t>& segs, const uint8_t* const* src,
+                        uint8_t* const* dst, bool seg_word) {
+  const int n = c->k + c->m;
+  int o0 = 0;
+  for (const RtChunk& ch : p.chunks) {
+    const bool rtb = cec::rt_takes_rtb(c->opts, ch.nob, ch.nin);  // as launch_chunk
+    PtrLaunch& l = ptr_launch_of(launches, rtb && ch.nob <= 4 ? 1 : 2, ch.nob,
+                                 (uint32_t)(1 + ch.nin + ch.nob + (seg_word ? 1 : 0)));
+    for (uint32_t s : segs) {
+      const size_t r0 = l.rows.size();
+      l.rows.resize(r0 + l.rs, 0);
+      uint64_t* r = l.rows.data() + r0;
+      if (seg_word) r[l.rs - 1] = s;
+      r[0] = (uint64_t)(uintptr_t)ch.dev;
+      for (int j = 0; j < ch.nin; ++j) r[1 + j] = (uint64_t)(uintptr_t)src[(size_t)s * n + p.in_idx[j]];
+      for (int o = 0; o < ch.nout; ++o)
+        r[1 + ch.nin + o] = (uint64_t)(uintptr_t)dst[(size_t)s * n + p.out_idx[o0 + o]];
+    }
+    o0 += ch.nout;
+  }
+}
+
+// Upload the rows of `launches` as one table and run them on `st`: pre() (an int code; what the
+// call enqueues ahead of its kernels) once the table and the programs' uploads `up` are complete,
+// then run(launch, its rows on the device, their count) per launch. The table is retired behind
+// the launches. Without rows nothing happens (pre() is not called).
+extern "C++" template <class Pre, class Run>
+static int run_ptr_table(cec_codec* c, const std::vector<PtrLaunch>& launches, Uploads& up,
+                         hipStream_t st, Pre pre, Run run) {
+  size_t words = 0;
+  for (const auto& l : launches) words += l.rows.size();
+  if (!words) return CEC_OK;
+  std::vector<uint64_t> host;
+  host.reserve(words);
+  for (const auto& l : launches) host.insert(host.end(), l.rows.begin(), l.rows.end());
+  void* d = nullptr;
+  const size_t bytes = words * sizeof(uint64_t);
+  int rc = c->pool.alloc(bytes, &d);
+  if (rc) return rc;
+  hipError_t e = hipMemcpyAsync(d, host.data(), bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the programs' uploads too
+  if (e != hipSuccess) {
+    c->pool.retire(d, bytes);
+    return set_err(CEC_EHIP, std::string("table upload: ") + hipGetErrorString(e));
+  }
+  up.arena.reset();
+  if ((rc = pre())) {
+    c->pool.retire(d, bytes);
+    return rc;
+  }
+  const uint64_t* tab = static_cast<const uint64_t*>(d);
+  for (const auto& l : launches) {
+    run(l, tab, (uint32_t)(l.rows.size() / l.rs));
+    rc = check_launch();
+    if (rc) break;
+    tab += l.rows.size();
+  }
+  const int mrc = c->pool.mark(st);  // the table and the programs stay until these complete
+  c->pool.retire(d, bytes);
+  return rc ? rc : mrc;
+}
+
+// cec_reconstruct_ptrs, cec_encode_ptrs and, with `d_ok`, cec_verify_ptrs. There `dst` names
+// expectations: the same programs and rows, run by the compare forms of the kernels, which read
+// what dst names and write only d_ok (preset to 1 here, behind the validation). Their rows also
+// hold the segment index, see launch_vptrs_*.
 static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_t* const* dst,
                                  size_t nseg, size_t shard_len, hipStream_t st,
                                  uint8_t* d_ok = nullptr) {
@@ -1459,27 +1571,15 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
   const bool vec_ok = (bits & 15) == 0;
   // launches: RS(2,1) rows for the compile-time kernel; otherwise one launch per (kernel, bucket)
   // over the rows of every pattern's chunk of that kind
-  struct Launch {
-    int kind;  // 0: RS(2,1) compile-time, 1: bit-plane (k_rtb's cases), 2: general
-    int nob;
-    uint32_t rs;
-    std::vector<uint64_t> rows;
-  };
-  std::vector<Launch> launches;
-  auto launch_of = [&](int kind, int nob, uint32_t rs) -> Launch& {
-    for (auto& l : launches)
-      if (l.kind == kind && l.nob == nob && l.rs == rs) return l;
-    launches.push_back({kind, nob, rs, {}});
-    return launches.back();
-  };
+  std::vector<PtrLaunch> launches;
   // one launch's kernel: the store forms (rebuild, encode) or the compare forms (verify)
-  auto launch_store = [&](const Launch& l, const uint64_t* tab, uint32_t nrows) {
+  auto launch_store = [&](const PtrLaunch& l, const uint64_t* tab, uint32_t nrows) {
     if (l.kind == 0)
       cec::launch_ptrs_rs21(tab, nrows, shard_len, vec_ok, st);
     else if (l.kind != 1 || !cec::launch_ptrs_rtb(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st))
       cec::launch_ptrs_rt(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st);
   };
-  auto launch_compare = [&](const Launch& l, const uint64_t* tab, uint32_t nrows) {
+  auto launch_compare = [&](const PtrLaunch& l, const uint64_t* tab, uint32_t nrows) {
     if (l.kind == 0)
       cec::launch_vptrs_rs21(tab, nrows, shard_len, vec_ok, d_ok, st);
     else if (l.kind != 1 ||
@@ -1487,11 +1587,13 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
       cec::launch_vptrs_rt(tab, nrows, l.rs, l.nob, shard_len, vec_ok, d_ok, st);
   };
   const bool ct21 = k == 2 && c->m == 1 && !c->force_generic;
+  bool any_rows = false;
   for (const Group& g : groups) {
     const Program& p = *g.prog;
     if (!p.nout || g.segs.empty()) continue;
+    any_rows = true;
     if (ct21) {  // one lost shard: p.single
-      Launch& l = launch_of(0, 1, 4);
+      PtrLaunch& l = ptr_launch_of(launches, 0, 1, 4);
       for (uint32_t s : g.segs) {
         l.rows.push_back((uint64_t)(uintptr_t)src[(size_t)s * n + p.in_idx[0]]);
         l.rows.push_back((uint64_t)(uintptr_t)src[(size_t)s * n + p.in_idx[1]]);
@@ -1500,61 +1602,120 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
       }
       continue;
     }
-    int o0 = 0;
-    for (const RtChunk& ch : p.chunks) {
-      const bool rtb = cec::rt_takes_rtb(c->opts, ch.nob, ch.nin);  // as launch_chunk
-      Launch& l = launch_of(rtb && ch.nob <= 4 ? 1 : 2, ch.nob,
-                            (uint32_t)(1 + ch.nin + ch.nob + (d_ok ? 1 : 0)));
-      for (uint32_t s : g.segs) {
-        const size_t r0 = l.rows.size();
-        l.rows.resize(r0 + l.rs, 0);
-        uint64_t* r = l.rows.data() + r0;
-        if (d_ok) r[l.rs - 1] = s;
-        r[0] = (uint64_t)(uintptr_t)ch.dev;
-        for (int j = 0; j < ch.nin; ++j) r[1 + j] = (uint64_t)(uintptr_t)src[(size_t)s * n + p.in_idx[j]];
-        for (int o = 0; o < ch.nout; ++o)
-          r[1 + ch.nin + o] = (uint64_t)(uintptr_t)dst[(size_t)s * n + p.out_idx[o0 + o]];
-      }
-      o0 += ch.nout;
-    }
+    add_rt_rows(c, launches, p, g.segs, src, dst, d_ok != nullptr);
   }
-  size_t words = 0;
-  for (const auto& l : launches) words += l.rows.size();
-  int rc = CEC_OK;
-  if (words) {
-    std::vector<uint64_t> host;
-    host.reserve(words);
-    for (const auto& l : launches) host.insert(host.end(), l.rows.begin(), l.rows.end());
-    void* d = nullptr;
-    const size_t bytes = words * sizeof(uint64_t);
-    rc = c->pool.alloc(bytes, &d);
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(d, host.data(), bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the programs' uploads too
-    if (e != hipSuccess) {
-      c->pool.retire(d, bytes);
-      return set_err(CEC_EHIP, std::string("table upload: ") + hipGetErrorString(e));
-    }
-    up.arena.reset();
-    if (d_ok && (e = hipMemsetAsync(d_ok, 1, nseg, st)) != hipSuccess) {
-      c->pool.retire(d, bytes);
-      return set_err(CEC_EHIP, std::string("verify: ") + hipGetErrorString(e));
-    }
-    const uint64_t* tab = static_cast<const uint64_t*>(d);
-    for (const auto& l : launches) {
-      const uint32_t nrows = (uint32_t)(l.rows.size() / l.rs);
-      if (d_ok) launch_compare(l, tab, nrows);
-      else launch_store(l, tab, nrows);
-      rc = check_launch();
-      if (rc) break;
-      tab += l.rows.size();
-    }
-    const int mrc = c->pool.mark(st);  // the table and the programs stay until these complete
-    c->pool.retire(d, bytes);
-    if (!rc) rc = mrc;
-  } else if (d_ok) {  // no segment has an expectation: every flag is 1
+  auto preset_ok = [&]() -> int {
+    if (!d_ok) return CEC_OK;
     const hipError_t e = hipMemsetAsync(d_ok, 1, nseg, st);
-    if (e != hipSuccess) rc = set_err(CEC_EHIP, std::string("verify: ") + hipGetErrorString(e));
+    return e == hipSuccess ? CEC_OK
+                           : set_err(CEC_EHIP, std::string("verify: ") + hipGetErrorString(e));
+  };
+  int rc = CEC_OK;
+  if (any_rows)
+    rc = run_ptr_table(c, launches, up, st, preset_ok,
+                       [&](const PtrLaunch& l, const uint64_t* tab, uint32_t nrows) {
+                         if (d_ok) launch_compare(l, tab, nrows);
+                         else launch_store(l, tab, nrows);
+                       });
+  else  // no segment has an expectation: every flag is 1
+    rc = preset_ok();
+  evict_decode(c);
+  return rc;
+}
+
+// cec_reconstruct_partial_ptrs: the sibling of the above for partial rebuilds. A segment's program
+// comes through get_partial (the decode rows of its pattern restricted to the held survivors,
+// and to the wanted outputs), its rows go to the run-time kernels whatever the code, and with
+// `accumulate` those are the accumulate forms. A segment with wanted outputs and no held survivor
+// has no program: its outputs are cleared (or, with accumulate, left alone).
+static int partial_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_t* const* dst,
+                             const uint8_t* present, size_t nseg, size_t shard_len,
+                             bool accumulate, hipStream_t st) {
+  const int n = c->k + c->m, k = c->k;
+  struct Group {
+    ProgPtr prog;  // null: no held survivor
+    std::vector<uint32_t> segs;
+  };
+  std::unordered_map<std::string, size_t> gidx;
+  std::vector<Group> groups;
+  Uploads up{c->stream, c->arena};  // synchronised once, with the table's upload
+  std::string key(3 * (size_t)n, '\0');  // present, held, wanted
+  uintptr_t bits = 0;  // OR of every address read or written: the alignment of the call
+  std::unordered_set<uintptr_t> seen;  // every wanted dst of the call
+  std::vector<uint8_t*> zeros;         // wanted dst of segments without a held survivor
+  for (size_t s = 0; s < nseg; ++s) {
+    const uint8_t* const* sp = src + s * n;
+    uint8_t* const* dp = dst + s * n;
+    const uint8_t* pr = present + s * n;
+    int np = 0;
+    bool wanted = false;
+    for (int i = 0; i < n; ++i) {
+      if (sp[i] && !pr[i]) return set_err(CEC_EINVAL, "a shard flagged absent is held");
+      key[i] = pr[i] ? 1 : 0;
+      key[n + i] = sp[i] ? 1 : 0;
+      key[2 * n + i] = !pr[i] && dp[i] ? 1 : 0;
+      np += key[i];
+      wanted |= key[2 * n + i] != 0;
+    }
+    if (!wanted) continue;  // nothing wanted: no row, no work, shards not counted
+    if (np < k) return set_err(CEC_ETOOFEW, "fewer than k shards present");
+    auto it = gidx.find(key);
+    if (it == gidx.end()) {
+      const uint8_t* f = reinterpret_cast<const uint8_t*>(key.data());
+      uint8_t rd[cec::kMaxShards];
+      if (!cec::survivor_set(k, c->m, f, rd))
+        return set_err(CEC_ETOOFEW, "fewer than k shards present");
+      bool held = false;
+      for (int i = 0; i < n; ++i) held |= rd[i] && f[n + i];
+      ProgPtr p;
+      if (held) {
+        int rc = get_partial(c, f, f + n, false, &p, &up.arena, nullptr, f + 2 * n);
+        if (rc) return rc;
+      }
+      it = gidx.emplace(key, groups.size()).first;
+      groups.push_back({p, {}});
+    }
+    Group& g = groups[it->second];
+    for (int i = 0; i < n; ++i) {
+      if (!key[2 * n + i]) continue;
+      if (!seen.insert((uintptr_t)dp[i]).second)
+        return set_err(CEC_EINVAL, "a destination is named twice");
+      if (!g.prog && !accumulate) zeros.push_back(dp[i]);
+    }
+    if (!g.prog) continue;
+    const Program& p = *g.prog;
+    const int nin = p.chunks[0].nin;  // the held survivors, in cec_survivors order
+    for (int o = 0; o < p.nout; ++o) {
+      const uint8_t* d = dp[p.out_idx[o]];
+      bits |= (uintptr_t)d;
+      for (int j = 0; j < nin; ++j)
+        if (d == sp[p.in_idx[j]])
+          return set_err(CEC_EINVAL, "a destination is a held survivor of its own segment");
+    }
+    for (int j = 0; j < nin; ++j) bits |= (uintptr_t)sp[p.in_idx[j]];
+    g.segs.push_back((uint32_t)s);
+  }
+  const bool vec_ok = (bits & 15) == 0;
+  std::vector<PtrLaunch> launches;
+  for (const Group& g : groups)
+    if (g.prog && !g.segs.empty()) add_rt_rows(c, launches, *g.prog, g.segs, src, dst, false);
+  int rc = run_ptr_table(
+      c, launches, up, st, [] { return (int)CEC_OK; },
+      [&](const PtrLaunch& l, const uint64_t* tab, uint32_t nrows) {
+        if (accumulate) {
+          if (l.kind != 1 ||
+              !cec::launch_xptrs_rtb(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st))
+            cec::launch_xptrs_rt(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st);
+        } else if (l.kind != 1 ||
+                   !cec::launch_ptrs_rtb(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st)) {
+          cec::launch_ptrs_rt(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st);
+        }
+      });
+  for (uint8_t* z : zeros) {  // zero is the neutral element of the exchange's sum
+    if (rc) break;
+    const hipError_t e = hipMemsetAsync(z, 0, shard_len, st);
+    if (e != hipSuccess)
+      rc = set_err(CEC_EHIP, std::string("partial: ") + hipGetErrorString(e));
   }
   evict_decode(c);
   return rc;
@@ -1598,6 +1759,60 @@ int cec_verify_ptrs(cec_codec* c, const uint8_t* const* src, const uint8_t* cons
   // the expectations sit where a rebuild's destinations do; the compare kernels only read them
   return reconstruct_ptrs_impl(c, src, const_cast<uint8_t* const*>(expect), nseg, shard_len,
                                pick_stream(c, hip_stream), d_ok);
+}
+
+int cec_reconstruct_partial_ptrs(cec_codec* c, const uint8_t* const* src, uint8_t* const* dst,
+                                 const uint8_t* present, size_t nseg, size_t shard_len,
+                                 int accumulate, void* hip_stream) {
+  if (!c || (nseg && (!src || !dst || !present))) return set_err(CEC_EINVAL, "null");
+  if (int rc = check_batch(nseg, shard_len)) return rc;
+  if (nseg == 0) return CEC_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  return partial_ptrs_impl(c, src, dst, present, nseg, shard_len, accumulate != 0,
+                           pick_stream(c, hip_stream));
+}
+
+int cec_xor_ptrs(cec_codec* c, uint8_t* const* dst, const uint8_t* const* src, size_t nrows,
+                 size_t nsrc, size_t len, void* hip_stream) {
+  if (!c) return set_err(CEC_EINVAL, "null");
+  if (len == 0 || nrows == 0 || nsrc == 0) return CEC_OK;
+  if (!dst || !src) return set_err(CEC_EINVAL, "null");
+  if (nrows > 0x7fffffffull || nsrc > 0x7ffffffeull)
+    return set_err(CEC_EINVAL, "too many rows or sources");
+  if ((len + 255) / 256 > 0x7fffffffull) return set_err(CEC_EINVAL, "len too large (> 512 GiB)");
+  // every address is checked, also those of rows that get no work: the arrays are then wrong
+  // whichever rows run
+  std::unordered_set<uintptr_t> dsts;
+  for (size_t r = 0; r < nrows; ++r)
+    if (dst[r] && !dsts.insert((uintptr_t)dst[r]).second)
+      return set_err(CEC_EINVAL, "a destination is named twice");
+  for (size_t i = 0; i < nrows * nsrc; ++i)
+    if (src[i] && dsts.count((uintptr_t)src[i]))
+      return set_err(CEC_EINVAL, "a source is a destination of the call");
+  std::vector<PtrLaunch> launches(1);
+  PtrLaunch& l = launches[0];
+  l = {3, 0, (uint32_t)(nsrc + 1), {}};  // rows {dst, nsrc sources}, NULL sources kept as 0
+  uintptr_t bits = 0;
+  for (size_t r = 0; r < nrows; ++r) {
+    if (!dst[r]) continue;
+    const uint8_t* const* sp = src + r * nsrc;
+    if (std::all_of(sp, sp + nsrc, [](const uint8_t* p) { return !p; })) continue;
+    l.rows.push_back((uint64_t)(uintptr_t)dst[r]);
+    bits |= (uintptr_t)dst[r];
+    for (size_t j = 0; j < nsrc; ++j) {
+      l.rows.push_back((uint64_t)(uintptr_t)sp[j]);
+      bits |= (uintptr_t)sp[j];
+    }
+  }
+  if (l.rows.empty()) return CEC_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, hip_stream);
+  const bool vec_ok = (bits & 15) == 0;
+  Uploads up{c->stream, c->arena};
+  return run_ptr_table(c, launches, up, st, [] { return (int)CEC_OK; },
+                       [&](const PtrLaunch& x, const uint64_t* tab, uint32_t n) {
+                         cec::launch_xor_rows(tab, n, (uint32_t)nsrc, len, vec_ok, st);
+                       });
 }
 
 int cec_reconstruct_partial_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size_t nseg,

@@ -159,6 +159,13 @@ bool launch_vptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob,
                       bool vec_ok, uint8_t* ok, hipStream_t st);
 void launch_vptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
                      bool vec_ok, uint8_t* ok, hipStream_t st);
+// The accumulate forms of the two run-time ones (cec_reconstruct_partial_ptrs with accumulate):
+// rows as in the store forms; the len bytes at every output address are read, XORed with the
+// product and written back.
+bool launch_xptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
+                      bool vec_ok, hipStream_t st);
+void launch_xptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
+                     bool vec_ok, hipStream_t st);
 
 // SHA-256 of `n` equal-length buffers, written as 64 lowercase hex characters each into
 // `hex_out` (device, n * 64 bytes). If `ptrs` is null, buffer i is shard (i % nshards) of
@@ -209,6 +216,11 @@ void launch_chunk_gather(const Layout& L, int nshards, uint64_t nfrag, const uin
 // XOR reduction (xor.hip): dst[0..len) ^= src[j * stride ..][0..len) for j < nsrc.
 void launch_xor_reduce(uint8_t* dst, const uint8_t* src, uint32_t nsrc, uint64_t stride,
                        uint64_t len, hipStream_t st);
+// Scattered form (cec_xor_ptrs): row r of the device table `tab` is {dst, nsrc sources}, 1 + nsrc
+// words; dst[0..len) ^= the len bytes at every non-zero source word. vec_ok: every address of the
+// table is 16-byte aligned (16-byte columns and a byte tail; else byte-wise).
+void launch_xor_rows(const uint64_t* tab, uint32_t nrows, uint32_t nsrc, uint64_t len,
+                     bool vec_ok, hipStream_t st);
 
 // Parity accumulation (acc.hip; cec_encode_idx_batch, cec_update_batch): for every segment s and
 // output o < nout

@@ -825,6 +825,22 @@ struct CmpSink {
     bad = 0;
   }
 };
+// XorSink (cec_reconstruct_partial_ptrs with accumulate) adds the product to what p holds: the
+// column at p is loaded with the load flavour of the inputs, XORed with the product and stored
+// back, a read-modify-write of exactly the bytes StoreSink writes. A lane owns its columns, so
+// nothing orders the load against another lane's store.
+struct XorSink {
+  template <bool NT, class TV, class Ptr>
+  __device__ __forceinline__ void col(Ptr p, TV y) { stv<NT, TV>(p, ldv<NT, TV>(p) ^ y); }
+  template <class Ptr>
+  struct Byte {
+    Ptr p;
+    __device__ __forceinline__ void operator=(uint8_t y) { *p = (uint8_t)(*p ^ y); }
+  };
+  template <class Ptr>
+  __device__ __forceinline__ Byte<Ptr> at(Ptr p) { return {p}; }
+  __device__ __forceinline__ void flush() {}
+};
 
 // Where a workgroup row of the run-time products finds its program chunk P and its shards: key(j)
 // names input j of the program, in(key) / out(o) give a shard's address. The index type of key
@@ -1987,6 +2003,44 @@ void launch_vptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, 
     for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
       hipLaunchKernelGGL((k_ptrtv<NOB, U, TV>), dim3(gx, ny), dim3(256), 0, st, tab, r0, rs, len,
                          vec_ok ? 1 : 0, ok);
+    });
+  });
+}
+
+// The accumulate forms (cec_reconstruct_partial_ptrs with accumulate): the same products with
+// XorSink, so every output address of a row is read, XORed with the product and written back.
+// Rows are those of the store forms, {program chunk, nin inputs, nout outputs}. Partials always
+// take the run-time kernels, so RS(2,1) has no compile-time form here.
+template <int NOB, int U, class TV>
+__global__ __launch_bounds__(256) void k_ptrtx(const uint64_t* __restrict__ tab, uint32_t row0,
+                                               uint32_t rs, uint64_t len, int vec_ok) {
+  rt_body<NOB, U, TV, TableAddr>(TableAddr(tab, row0 + blockIdx.y, rs, len), vec_ok, XorSink{});
+}
+
+template <int NOB, class TV, int PF>
+__global__ __launch_bounds__(256) void k_ptrbx(const uint64_t* __restrict__ tab, uint32_t row0,
+                                               uint32_t rs, uint64_t len, int vec_ok) {
+  rtb_body<NOB, TV, PF, TableAddr>(TableAddr(tab, row0 + blockIdx.y, rs, len), vec_ok, XorSink{});
+}
+
+bool launch_xptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
+                      bool vec_ok, hipStream_t st) {
+  return rtb_dispatch(nob, [&]<int NOB, class TV, int PF>(RtbShape<NOB, TV, PF>) {
+    const unsigned gx = rt_grid_x(len, sizeof(TV), 1, vec_ok);
+    for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
+      hipLaunchKernelGGL((k_ptrbx<NOB, TV, PF>), dim3(gx, ny), dim3(256), 0, st, tab, r0, rs, len,
+                         vec_ok ? 1 : 0);
+    });
+  });
+}
+
+void launch_xptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
+                     bool vec_ok, hipStream_t st) {
+  rt_dispatch(nob, [&]<int NOB, int U, class TV>(RtShape<NOB, U, TV>) {
+    const unsigned gx = rt_grid_x(len, sizeof(TV), U, vec_ok);
+    for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
+      hipLaunchKernelGGL((k_ptrtx<NOB, U, TV>), dim3(gx, ny), dim3(256), 0, st, tab, r0, rs, len,
+                         vec_ok ? 1 : 0);
     });
   });
 }

@@ -45,6 +45,60 @@ void launch_xor_reduce(uint8_t* dst, const uint8_t* src, uint32_t nsrc, uint64_t
                        nsrc, stride, len);
 }
 
+// The scattered form (cec_xor_ptrs): every workgroup row (blockIdx.y) owns one row {dst, nsrc
+// sources} of 64-bit words in a device table, so destinations and partials lie wherever the
+// caller has them (receive buffers, output tensors) and rows may have different numbers of
+// partials: a zero word is skipped. The row is read through the constant address space, as the
+// pointer tables of kernels.hip are: the addresses arrive as wave-uniform scalar loads, the skip
+// is a wave-uniform branch, and the words become address_space(1) pointers, so the accesses stay
+// global_load / global_store. One lane owns 16 bytes, streaming as above; the last block of a row
+// also takes the byte tail, and with vec_ok == 0 (some address of the call is not 16-byte aligned)
+// the grid covers the row byte by byte.
+typedef const uint64_t __attribute__((address_space(4))) xcu64;
+typedef uint8_t __attribute__((address_space(1))) xgu8;
+typedef u32x4 __attribute__((address_space(1))) xgv16;
+
+__global__ __launch_bounds__(256) void k_xor_rows(const uint64_t* __restrict__ tab, uint32_t row0,
+                                                  uint32_t nsrc, uint64_t len, int vec_ok) {
+  const xcu64* __restrict__ row =
+      (const xcu64*)(uintptr_t)tab + ((uint64_t)row0 + blockIdx.y) * ((uint64_t)nsrc + 1);
+  xgu8* const dst = (xgu8*)row[0];
+  if (vec_ok) {
+    const uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v < len / 16) {
+      u32x4 acc = __builtin_nontemporal_load((const xgv16*)dst + v);
+      for (uint32_t j = 0; j < nsrc; ++j) {
+        const uint64_t a = row[1 + j];
+        if (a) acc ^= __builtin_nontemporal_load((const xgv16*)a + v);  // wave-uniform
+      }
+      __builtin_nontemporal_store(acc, (xgv16*)dst + v);
+    }
+    if (!(len % 16) || blockIdx.x != gridDim.x - 1) return;
+  }
+  // byte path: whole row (vec_ok == 0, grid covers len) or the tail (last block)
+  const uint64_t i = vec_ok ? (len - len % 16) + threadIdx.x
+                            : (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= len) return;
+  uint8_t acc = dst[i];
+  for (uint32_t j = 0; j < nsrc; ++j) {
+    const uint64_t a = row[1 + j];
+    if (a) acc ^= ((const xgu8*)a)[i];
+  }
+  dst[i] = acc;
+}
+
+void launch_xor_rows(const uint64_t* tab, uint32_t nrows, uint32_t nsrc, uint64_t len,
+                     bool vec_ok, hipStream_t st) {
+  if (len == 0 || nsrc == 0 || nrows == 0) return;
+  uint64_t gx = vec_ok ? (len / 16 + 255) / 256 : (len + 255) / 256;
+  if (gx == 0) gx = 1;  // shorter than one column: the tail's block
+  for (uint32_t r0 = 0; r0 < nrows; r0 += 65535) {
+    const uint32_t ny = nrows - r0 < 65535 ? nrows - r0 : 65535;
+    hipLaunchKernelGGL(k_xor_rows, dim3((uint32_t)gx, ny), dim3(256), 0, st, tab, r0, nsrc, len,
+                       vec_ok ? 1 : 0);
+  }
+}
+
 // Per-segment equality of two [nseg][seg_bytes] device arrays (cec_verify_batch: recomputed
 // parity against the stored parity): ok[seg] was set to 1 before; a lane that finds a differing
 // 16-byte piece (or byte, unaligned) stores 0 there. Read-only streaming otherwise.

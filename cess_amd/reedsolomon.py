@@ -466,6 +466,114 @@ class Encoder:
                                             self._device_stream(stream)), "VerifyDeviceBatch")
         return d_ok
 
+    def ReconstructPartialDevice(self, shards: Sequence, present, out=None,
+                                 accumulate: bool = False, stream=None) -> dict:
+        """Partial rebuild of one segment in place (cec_reconstruct_partial_ptrs). `shards` is a
+        list of k + m 1-D uint8 device tensors or None: non-None means this caller holds the
+        shard. `present` is the segment's erasure pattern as every party knows it (k + m flags).
+        Every output receives the contribution of the held survivors only; the XOR of the outputs
+        over a partition of the survivors is the rebuilt shard (XorDevice). The lost shards named
+        in `out` (a list or {index: tensor}, as in ReconstructDevice) are the outputs; with
+        out=None every lost shard is allocated. accumulate=True XORs the partial into what the
+        outputs hold and requires `out` (ErrInvalidInput otherwise). Returns {index: tensor}.
+        Enqueued on `stream` (default: torch's current stream) and not waited for."""
+        import torch
+        n = self.Shards
+        if accumulate and out is None:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        if len(shards) != n or len(present) != n:
+            raise ErrTooFewShards(ErrTooFewShards.__doc__)
+        lost = [i for i in range(n) if not present[i]]
+        if out is None:
+            size = self._check_device_shards([s for s in shards if s is not None])
+            dev = torch.device("cuda", self.device)
+            outs = {i: torch.empty(size, dtype=torch.uint8, device=dev) for i in lost}
+        else:
+            get = out.get if isinstance(out, dict) else (lambda i: out[i] if i < len(out) else None)
+            outs = {i: get(i) for i in lost if get(i) is not None}
+        self.ReconstructPartialDeviceBatch([shards], [present], [outs], accumulate, stream)
+        return outs
+
+    def ReconstructPartialDeviceBatch(self, segments: Sequence, present, outs,
+                                      accumulate: bool = False, stream=None) -> None:
+        """ReconstructPartialDevice for many segments in one call: `segments[s]` the k + m held
+        tensors or None, `present[s]` the k + m flags, `outs[s]` a list or {index: tensor} of
+        the wanted lost shards' tensors (None: nothing wanted of that segment). Every tensor must
+        be a contiguous 1-D uint8 tensor of one length on the codec's GPU (TypeError otherwise).
+        With accumulate=False an output of a segment without a held survivor is zeroed, with
+        accumulate=True it is left as it is."""
+        import torch
+        nseg, n = len(segments), self.Shards
+        if len(present) != nseg or len(outs) != nseg:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        if nseg == 0:
+            return
+        dev = torch.device("cuda", self.device)
+        src = (c_void_p * (nseg * n))()
+        dst = (c_void_p * (nseg * n))()
+        flags = (c_uint8 * (nseg * n))()
+        used = []
+
+        def addr(t):
+            if t.device != dev:  # (_dev_ptr refuses host and strided tensors)
+                raise TypeError("device shards must live on the codec's GPU")
+            used.append(t)
+            return _dev_ptr(t)
+
+        for s, shards in enumerate(segments):
+            if len(shards) != n or len(present[s]) != n:
+                raise ErrTooFewShards(ErrTooFewShards.__doc__)
+            out = outs[s]
+            for i in range(n):
+                flags[s * n + i] = 1 if present[s][i] else 0
+                if shards[i] is not None:
+                    src[s * n + i] = addr(shards[i])
+                if out is None or present[s][i]:
+                    continue
+                t = out.get(i) if isinstance(out, dict) else (out[i] if i < len(out) else None)
+                if t is not None:
+                    dst[s * n + i] = addr(t)
+        size = self._check_device_shards(used)
+        check(self._lib.cec_reconstruct_partial_ptrs(
+            self._h, src, dst, flags, nseg, size, 1 if accumulate else 0,
+            self._device_stream(stream)), "ReconstructPartialDevice")
+
+    def XorDevice(self, dsts: Sequence, srcs: Sequence, stream=None) -> None:
+        """GF(2^8) sum of scattered device tensors (cec_xor_ptrs), the combine step of the
+        partials: dsts[r] ^= XOR of the tensors in srcs[r]. `dsts` is a list of 1-D uint8 device
+        tensors or None (a None row is skipped), `srcs` a list of lists of tensors or None (rows
+        may differ in length; a None entry is skipped). Every tensor must be contiguous, of one
+        length and on the codec's GPU (TypeError otherwise). Enqueued on `stream` (default:
+        torch's current stream) and not waited for."""
+        import torch
+        nrows = len(dsts)
+        if len(srcs) != nrows:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        nsrc = max((len(r) for r in srcs if r is not None), default=0)
+        if nrows == 0 or nsrc == 0:
+            return
+        dev = torch.device("cuda", self.device)
+        d = (c_void_p * nrows)()
+        a = (c_void_p * (nrows * nsrc))()
+        used = []
+        for r in range(nrows):
+            row = [dsts[r]] + list(srcs[r] or [])
+            for j, t in enumerate(row):
+                if t is None:
+                    continue
+                if t.device != dev:
+                    raise TypeError("device shards must live on the codec's GPU")
+                used.append(t)
+                if j == 0:
+                    d[r] = _dev_ptr(t)
+                else:
+                    a[r * nsrc + j - 1] = _dev_ptr(t)
+        if not used:
+            return
+        size = self._check_device_shards(used)
+        check(self._lib.cec_xor_ptrs(self._h, d, a, nrows, nsrc, size,
+                                     self._device_stream(stream)), "XorDevice")
+
     def _check_device_shards(self, tensors) -> int:
         import torch
         size = 0

@@ -91,8 +91,9 @@ int cec_verify(cec_codec* codec, uint8_t* const* shards, size_t shard_len, int* 
  * cec_reconstruct_batch of RS(2,1) with one pattern (per_segment = 0). Every other rebuild reads
  * a decode program from the codec's cache, which may evict it while a graph still points at it:
  * do not capture those, nor cec_reconstruct_some_batch, nor the pointer-table calls
- * (cec_reconstruct_ptrs, cec_encode_ptrs, cec_verify_ptrs: their kernels read a codec-owned
- * table that is retired once the call's launches complete). A single 16 MiB RS(2,1) segment's
+ * (cec_reconstruct_ptrs, cec_encode_ptrs, cec_verify_ptrs, cec_reconstruct_partial_ptrs,
+ * cec_xor_ptrs: their kernels read a codec-owned table that is retired once the call's launches
+ * complete). A single 16 MiB RS(2,1) segment's
  * encode + three rebuilds: 29.5 us eagerly, 24.8 us as one graph (profiles/r05/graph_probe.log). */
 int cec_encode_batch(cec_codec* codec, const uint8_t* d_data, uint8_t* d_parity, size_t nseg,
                      size_t shard_len, void* hip_stream);
@@ -204,6 +205,66 @@ int cec_verify_ptrs(cec_codec* codec, const uint8_t* const* src, const uint8_t* 
  * device holding the buffers (no codec: the caller's current device and stream decide). */
 int cec_xor_batch(uint8_t* d_dst, const uint8_t* d_src, size_t nsrc, size_t src_stride,
                   size_t len, void* hip_stream);
+/* Partial rebuild of scattered shards, in place: cec_reconstruct_partial_batch without the batch.
+ * With n = k+m: present is a HOST array of nseg*n flags, the erasure pattern of each segment as
+ * every party of the exchange knows it (its survivors are cec_survivors of its row). src, dst:
+ * HOST arrays of nseg*n DEVICE pointers laid out as in cec_reconstruct_ptrs. src[s*n+i] non-NULL =
+ * the caller holds shard i of segment s at that address. dst[s*n+i] non-NULL at a shard flagged
+ * absent = that shard is a wanted output (shard_len bytes); dst entries of present shards are
+ * ignored. Every wanted output i receives XOR over the held survivors j of D[i][j] * shard_j, D[i]
+ * the decode row cec_decode_rows gives for the pattern. XOR-ing the results over any partition of
+ * a segment's survivors gives the rebuilt shard (cec_xor_ptrs), as with the batch form.
+ *  - accumulate == 0: dst = partial. A segment with wanted outputs and no held survivor gets
+ *    zeros written (the neutral element, as in the batch form).
+ *    accumulate != 0: dst ^= partial, a read-modify-write of exactly the shard_len bytes at each
+ *    wanted dst. A segment with no held survivor gets no workgroup and is not touched.
+ *  - Reads: only held shards that are survivors of their segment, and with accumulate the wanted
+ *    dst. A held shard that is present but not one of the k survivors is never read and may hold
+ *    anything.
+ *  - Writes: nothing but the shard_len bytes at each wanted dst. A segment with no wanted output
+ *    costs nothing (no workgroup, and its shards are not counted).
+ *  - Validation: everything is validated before anything is enqueued; on an error no byte is
+ *    written. CEC_EINVAL: a NULL codec; a NULL array with nseg > 0; src non-NULL at a shard
+ *    flagged absent (the table and the flags are out of step); a wanted dst equal to a held
+ *    survivor address of its own segment; the same wanted dst address twice in one call (two rows
+ *    would race on it). Equal addresses are what is checked: ranges that overlap partially are
+ *    the caller's duty to avoid. CEC_ETOOFEW: a segment with a wanted output and fewer than k
+ *    shards flagged present. CEC_ESHARDLEN: shard_len == 0. nseg == 0: CEC_OK.
+ *  - Pointer arrays: all three arrays belong to the caller again on return. The device table comes
+ *    from the codec's pool and is retired once the launches complete, as in cec_reconstruct_ptrs;
+ *    the work is enqueued on hip_stream and not waited for.
+ *  - Alignment: any alignment and any shard_len >= 1 is correct. When every address read or
+ *    written is 16-byte aligned the kernels take vector columns with a byte tail, otherwise the
+ *    whole call runs byte-wise.
+ *  - HIP graph capture: not capturable, for the reasons given at cec_reconstruct_ptrs.
+ * Programs come from the codec's LRU cache under the partial keys of
+ * cec_reconstruct_partial_batch extended by the wanted-output mask: a call whose outputs are every
+ * lost shard shares its entry with the batch form of the same pattern and held set. Every geometry
+ * runs the table-addressed run-time kernels (the store forms, or their accumulate forms): RS(2,1)
+ * too, where a partial of one survivor is one multiplication and no closed form exists, and
+ * RS(32,32), whose FFT-domain decoders never run partials. */
+int cec_reconstruct_partial_ptrs(cec_codec* codec, const uint8_t* const* src,
+                                 uint8_t* const* dst, const uint8_t* present, size_t nseg,
+                                 size_t shard_len, int accumulate, void* hip_stream);
+/* GF(2^8) addition of scattered device buffers, the combine step of the partials above where
+ * they were received: dst is a HOST array of nrows DEVICE pointers, src a HOST array of
+ * nrows*nsrc DEVICE pointers, and dst[r][0..len) ^= XOR over j < nsrc of src[r*nsrc+j][0..len).
+ * A NULL src entry is skipped (rows have different numbers of partials). A NULL dst[r], or a row
+ * with no source, gets no workgroup.
+ *  - Reads: the len bytes at every non-NULL src of a row with a dst, and at that dst.
+ *    Writes: nothing but the len bytes at those dst.
+ *  - Validation: before anything is enqueued; on an error no byte is written. CEC_EINVAL: a NULL
+ *    codec; a NULL array with work to do; the same dst address twice; any src address equal to
+ *    any dst address of the call (equal addresses are what is checked, partial overlaps are the
+ *    caller's duty). len == 0, nrows == 0 or nsrc == 0 is a no-op that returns CEC_OK, as in
+ *    cec_xor_batch.
+ *  - Pointer arrays, alignment, table: as cec_reconstruct_ptrs. Both arrays belong to the caller
+ *    again on return; 16-byte columns with a byte tail when every address in use is 16-byte
+ *    aligned, otherwise the whole call runs byte-wise; the device table comes from the codec's
+ *    pool and is retired once the launches complete, so the call is not capturable. The work is
+ *    enqueued on hip_stream and not waited for. */
+int cec_xor_ptrs(cec_codec* codec, uint8_t* const* dst, const uint8_t* const* src, size_t nrows,
+                 size_t nsrc, size_t len, void* hip_stream);
 /* ---- parity accumulated shard by shard (klauspost EncodeIdx and Update) -----------------------
  * Both are one primitive on the codec's encode matrix E (cec_matrix; row k+o is parity shard o):
  *   parity[o] ^= E[k+o][j] * x_j   for every o < m,

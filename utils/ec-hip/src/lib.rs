@@ -178,6 +178,13 @@ pub mod sys {
                                d_ok: *mut u8, stream: *mut c_void) -> c_int;
         pub fn cec_xor_batch(d_dst: *mut u8, d_src: *const u8, nsrc: usize, src_stride: usize,
                              len: usize, stream: *mut c_void) -> c_int;
+        pub fn cec_reconstruct_partial_ptrs(c: *mut cec_codec, src: *const *const u8,
+                                            dst: *const *mut u8, present: *const u8,
+                                            nseg: usize, shard_len: usize, accumulate: c_int,
+                                            stream: *mut c_void) -> c_int;
+        pub fn cec_xor_ptrs(c: *mut cec_codec, dst: *const *mut u8, src: *const *const u8,
+                            nrows: usize, nsrc: usize, len: usize,
+                            stream: *mut c_void) -> c_int;
         pub fn cec_encode_idx_batch(c: *mut cec_codec, d_shard: *const u8,
                                     shard_seg_stride: usize, idx: c_int, d_parity: *mut u8,
                                     nseg: usize, shard_len: usize, accumulate: c_int,
@@ -565,6 +572,46 @@ impl ReedSolomon {
         }
         check(cec_verify_ptrs(self.c, src.as_ptr(), expect.as_ptr(), src.len() / n, shard_len,
                               d_ok, stream))
+    }
+
+    /// Partial rebuild of scattered device shards in place (`cec_reconstruct_partial_ptrs`):
+    /// `src`, `dst` and `present` hold `nseg * (k + m)` entries, segment by segment. `present` is
+    /// the erasure pattern every party knows; a non-null `src` entry is a shard this caller holds;
+    /// a non-null `dst` entry of an absent shard receives XOR over the held survivors j of
+    /// D[i][j] * shard_j (`accumulate`: is XORed with it, a read-modify-write). XOR-ing the
+    /// partials over a partition of a segment's survivors gives the rebuilt shard (`xor_device`).
+    /// Enqueued on `stream` and not waited for; the slices may be reused as soon as the call
+    /// returns.
+    ///
+    /// # Safety
+    /// Every non-null address must be device memory of `shard_len` bytes on the codec's GPU that
+    /// stays valid until the stream has passed the call's work; wanted destinations must not
+    /// overlap each other or a held survivor.
+    pub unsafe fn reconstruct_partial_device(&self, src: &[*const u8], dst: &[*mut u8],
+                                             present: &[u8], shard_len: usize, accumulate: bool,
+                                             stream: *mut c_void) -> Result<(), Error> {
+        let n = self.k + self.m;
+        if src.len() != dst.len() || src.len() != present.len() || src.len() % n != 0 {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        check(cec_reconstruct_partial_ptrs(self.c, src.as_ptr(), dst.as_ptr(), present.as_ptr(),
+                                           src.len() / n, shard_len, accumulate as c_int, stream))
+    }
+
+    /// GF(2^8) sum of scattered device buffers (`cec_xor_ptrs`): `dst[r] ^= XOR of the non-null
+    /// entries of src[r * nsrc .. (r + 1) * nsrc]`, `len` bytes each. A null `dst[r]` or a row
+    /// without a source is skipped. Enqueued on `stream` and not waited for; both slices may be
+    /// reused as soon as the call returns.
+    ///
+    /// # Safety
+    /// Every non-null address must be device memory of `len` bytes on the codec's GPU that stays
+    /// valid until the stream has passed the call's work; no source may overlap a destination.
+    pub unsafe fn xor_device(&self, dst: &[*mut u8], src: &[*const u8], nsrc: usize, len: usize,
+                             stream: *mut c_void) -> Result<(), Error> {
+        if src.len() != dst.len() * nsrc {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        check(cec_xor_ptrs(self.c, dst.as_ptr(), src.as_ptr(), dst.len(), nsrc, len, stream))
     }
 
     /// The decode rows of the `required` lost shards of pattern `present` (`cec_decode_rows`):
