@@ -867,8 +867,11 @@ def test_c_abi_consumer(tmp_path):
 def test_runtime_kernels_agree(torch, cess, corc, k, m, ln, ne):
     """k_rth (Horner over input groups, run-time indices), k_rt (per-bit masks), k_rthx
     (Horner with index-mode XORs) and k_rtb (bit-plane accumulators, chunks of <= 4 outputs)
-    against the C oracle: encode and per-segment reconstruct of `ne` random erasures, vector body
-    and byte tail."""
+    against the C oracle: encode and per-segment reconstruct of `ne` random erasures. The batch
+    layout's shard stride is the length itself, so a length that is no multiple of 16 (of 4 for
+    k_rth and k_rthx) makes the whole launch run byte-wise (vec_ok == 0): those cases cover the
+    all-byte path, not a byte tail behind a vector body, and only the lengths that are multiples
+    of 16 run the vector body. Body plus tail, past one workgroup, is tests/test_gpu_layouts.py."""
     nseg = 3
     rng = np.random.default_rng(k * 1000 + ln + ne)
     data = rng.integers(0, 256, (nseg, k, ln), dtype=np.uint8)
@@ -1042,7 +1045,10 @@ def test_fftdec_dispatch_by_cost(torch, cess, corc, ne):
 @pytest.mark.parametrize("ne,ln", [(1, 4096 + 3), (2, (1 << 16) + 16), (3, 4096 + 3), (4, 999)])
 def test_rtb_tuning_shapes_agree(torch, cess, corc, ne, ln):
     """The tuning build's k_rtb shapes (column width x columns in flight, variants 40-49)
-    rebuild RS(32,32) erasures bit-exact: vector body and byte tail."""
+    rebuild RS(32,32) erasures bit-exact. At 4096 + 3 and 999 the batch layout's shard starts are
+    unaligned and the whole launch runs byte-wise (vec_ok == 0), whatever the shape; (1 << 16) + 16
+    runs the vector body without a tail. The product shapes' vector body followed by a byte tail
+    is tests/test_gpu_layouts.py."""
     k, m, nseg = 32, 32, 3
     rng = np.random.default_rng(77 + ne)
     data = rng.integers(0, 256, (nseg, k, ln), dtype=np.uint8)
