@@ -88,6 +88,10 @@ SIGNATURES = {
                                      c_size_t, c_int, c_void_p]),
     "cec_update_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,
                                  POINTER(c_uint8), c_void_p]),
+    "cec_encode_idx_ptrs": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_size_t,
+                                    c_size_t, c_int, c_void_p]),
+    "cec_update_ptrs": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p),
+                                POINTER(c_void_p), c_size_t, c_size_t, c_void_p]),
     "cec_encode_idx": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_void_p), c_size_t]),
     "cec_update": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_size_t]),
     "cec_sha256_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,

@@ -1,4 +1,5 @@
-// Parity accumulated shard by shard (cec_encode_idx_batch, cec_update_batch): the one primitive
+// Parity accumulated shard by shard (cec_encode_idx_batch, cec_update_batch, and on scattered
+// shards cec_encode_idx_ptrs, cec_update_ptrs: k_acc_ptrs below): the one primitive
 //   parity[o] ^= XOR_j c[j][o] * x_j        (overwrite mode: parity[o] = ...)
 // where x_j is a data shard (EncodeIdx) or old_j ^ new_j of a changed data shard (Update).
 //
@@ -78,8 +79,9 @@ __device__ __forceinline__ void st16(uint8_t* p, u32x4 v) {
 
 // The product over one lane's U columns. ld_in(which, slot, u): column u of input slot `slot` of
 // in_a (which = 0) or in_b (1); ld_par / st_par(o, u): column u of parity shard o.
-template <int NOB, int U, bool UPD, class T, class LI, class LP, class SP>
-__device__ __forceinline__ void acc_fold(const AccArgsK* __restrict__ K, uint32_t nin,
+// K: the launch's arguments in the kernarg segment (AccArgs or AccPtrArgs: slot, hb, coef).
+template <int NOB, int U, bool UPD, class T, class KA, class LI, class LP, class SP>
+__device__ __forceinline__ void acc_fold(const KA* __restrict__ K, uint32_t nin,
                                          uint32_t nout, bool accumulate, LI ld_in, LP ld_par,
                                          SP st_par) {
   T acc[NOB][U];
@@ -240,7 +242,129 @@ void run_acc_bucket(int nob, const AccArgs& a, uint64_t nseg, hipStream_t st) {
   }
 }
 
+// The table-addressed form (cec_encode_idx_ptrs, cec_update_ptrs): every workgroup row
+// (blockIdx.y) owns one row of 64-bit words in a device table, {nin input addresses [, the nin
+// new-data addresses (Update)], nout parity addresses}, rows `rs` words apart, so every shard lies
+// wherever the caller has it. The row is read through the constant address space and its words
+// become address_space(1) pointers (dev_util.h): scalar loads ahead of global_load / global_store.
+// The product, the column clamp and the byte tail are k_acc's.
+struct AccPtrArgs {
+  const uint64_t* tab;
+  uint64_t len;
+  uint32_t row0, rs, nin, nout, flags, pad_;
+  uint32_t slot[kAccMaxIn];                 // input j is word slot[j] of the row (its new bytes
+                                            // word nin + slot[j])
+  int32_t hb[kAccMaxIn];                    // as AccArgs
+  uint32_t coef[kAccMaxIn][kRtMaxOut / 4];  // as AccArgs
+};
+
+typedef const AccPtrArgs __attribute__((address_space(4))) AccPtrArgsK;
+typedef u32x4 __attribute__((address_space(1))) gv16;
+
+__device__ __forceinline__ u32x4 ld16(const gu8* p) {
+  return __builtin_nontemporal_load((const gv16*)p);
+}
+__device__ __forceinline__ void st16(gu8* p, u32x4 v) {
+  __builtin_nontemporal_store(v, (gv16*)p);
+}
+
+// Grid x: as k_acc; grid y: table rows from row0.
+template <int NOB, int U, bool UPD>
+__global__ __launch_bounds__(256) void k_acc_ptrs(AccPtrArgs a) {
+  const AccPtrArgsK* __restrict__ K =
+      (const AccPtrArgsK*)__builtin_amdgcn_kernarg_segment_ptr();  // the only argument: offset 0
+  const cu64* __restrict__ row = tab_row(a.tab, (uint64_t)a.row0 + blockIdx.y, a.rs);
+  const uint32_t par0 = UPD ? 2 * a.nin : a.nin;  // the row's first parity word
+  const bool accumulate = (a.flags & kAccAccumulate) != 0;
+  const bool vec = (a.flags & kAccVec16) != 0;
+  const uint64_t nvec = a.len / 16;
+  if (vec && nvec) {
+    // lanes past the last column read it again and store nothing, as in k_acc
+    const uint64_t base = (uint64_t)blockIdx.x * (256 * U) + threadIdx.x;
+    auto col = [&](int u) CEC_AI -> uint64_t {
+      const uint64_t v = base + (uint64_t)u * 256;
+      return (v < nvec ? v : nvec - 1) * 16;
+    };
+    auto ld_in = [&](int which, uint32_t slot, int u) CEC_AI -> u32x4 {
+      return ld16(gptr(row[slot + (which ? a.nin : 0)]) + col(u));
+    };
+    auto ld_par = [&](uint32_t o, int u) CEC_AI -> u32x4 {
+      return ld16(gptr(row[par0 + o]) + col(u));
+    };
+    auto st_par = [&](int o, int u, u32x4 y) CEC_AI {
+      if (base + (uint64_t)u * 256 < nvec) st16(gptr(row[par0 + o]) + col(u), y);
+    };
+    acc_fold<NOB, U, UPD, u32x4>(K, a.nin, a.nout, accumulate, ld_in, ld_par, st_par);
+  }
+  if (vec && (!(a.len % 16) || blockIdx.x != gridDim.x - 1)) return;
+  // byte path: the whole shard (grid covers len) or the tail after the last full column
+  const uint64_t i = vec ? (a.len - a.len % 16) + threadIdx.x
+                         : (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.len) return;
+  auto ld_in = [&](int which, uint32_t slot, int) CEC_AI -> uint32_t {
+    return gptr(row[slot + (which ? a.nin : 0)])[i];
+  };
+  auto ld_par = [&](uint32_t o, int) CEC_AI -> uint32_t { return gptr(row[par0 + o])[i]; };
+  auto st_par = [&](int o, int, uint32_t y) CEC_AI { gptr(row[par0 + o])[i] = (uint8_t)y; };
+  acc_fold<NOB, 1, UPD, uint32_t>(K, a.nin, a.nout, accumulate, ld_in, ld_par, st_par);
+}
+
+template <int NOB, bool UPD>
+void run_acc_ptrs(AccPtrArgs a, uint64_t nrows, hipStream_t st) {
+  constexpr int U = 1;
+  uint64_t gx = (a.flags & kAccVec16) ? (a.len / 16 + 256 * U - 1) / (256 * U) : (a.len + 255) / 256;
+  if (gx == 0) gx = 1;  // tail-only shard
+  for_y_slices(nrows, [&](uint32_t r0, uint32_t ny) {
+    a.row0 = r0;
+    hipLaunchKernelGGL((k_acc_ptrs<NOB, U, UPD>), dim3((unsigned)gx, ny), dim3(256), 0, st, a);
+  });
+}
+
+template <bool UPD>
+void run_acc_ptrs_bucket(int nob, const AccPtrArgs& a, uint64_t nrows, hipStream_t st) {
+  switch (nob) {
+    case 1: run_acc_ptrs<1, UPD>(a, nrows, st); break;
+    case 2: run_acc_ptrs<2, UPD>(a, nrows, st); break;
+    case 3: run_acc_ptrs<3, UPD>(a, nrows, st); break;
+    case 4: run_acc_ptrs<4, UPD>(a, nrows, st); break;
+    case 5: run_acc_ptrs<5, UPD>(a, nrows, st); break;
+    case 6: run_acc_ptrs<6, UPD>(a, nrows, st); break;
+    case 7: run_acc_ptrs<7, UPD>(a, nrows, st); break;
+    case 8: run_acc_ptrs<8, UPD>(a, nrows, st); break;
+    case 12: run_acc_ptrs<12, UPD>(a, nrows, st); break;
+    case 16: run_acc_ptrs<16, UPD>(a, nrows, st); break;
+    case 24: run_acc_ptrs<24, UPD>(a, nrows, st); break;
+    default: run_acc_ptrs<32, UPD>(a, nrows, st); break;
+  }
+}
+
 }  // namespace
+
+void launch_acc_ptrs(const uint64_t* tab, uint32_t nrows, const uint8_t* coef, int nin, int nout,
+                     bool update, bool accumulate, uint64_t len, bool vec_ok, hipStream_t st) {
+  if (nrows == 0 || len == 0 || nin <= 0 || nout <= 0 || nin > kAccMaxIn || nout > kRtMaxOut)
+    return;
+  AccPtrArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.tab = tab;
+  a.len = len;
+  a.rs = (uint32_t)((update ? 2 : 1) * nin + nout);
+  a.nin = (uint32_t)nin;
+  a.nout = (uint32_t)nout;
+  a.flags = (accumulate ? kAccAccumulate : 0) | (vec_ok ? kAccVec16 : 0);
+  for (int j = 0; j < nin; ++j) {
+    a.slot[j] = (uint32_t)j;
+    unsigned any = 0;
+    for (int o = 0; o < nout; ++o) {
+      const unsigned c = coef[(size_t)j * nout + o];
+      any |= c;
+      a.coef[j][o >> 2] |= (uint32_t)c << (8 * (o & 3));
+    }
+    a.hb[j] = any ? 31 - __builtin_clz(any) : -1;
+  }
+  if (update) run_acc_ptrs_bucket<true>(rt_bucket(nout), a, nrows, st);
+  else run_acc_ptrs_bucket<false>(rt_bucket(nout), a, nrows, st);
+}
 
 void launch_acc(const uint8_t* in_a, const uint8_t* in_b, uint64_t in_seg_stride,
                 uint64_t in_slot_stride, uint8_t* parity, uint64_t par_seg_stride,

@@ -1439,10 +1439,12 @@ int cec_decode_rows(int k, int m, const uint8_t* present, const uint8_t* require
 
 // One kernel launch of such a call and its rows of the table.
 struct PtrLaunch {
-  int kind;  // 0: RS(2,1) compile-time, 1: bit-plane (k_rtb's cases), 2: general, 3: cec_xor_ptrs
+  int kind;  // 0: RS(2,1) compile-time, 1: bit-plane (k_rtb's cases), 2: general, 3: cec_xor_ptrs,
+             // 4: parity accumulation (acc_ptrs_impl; never merged: see id)
   int nob;
   uint32_t rs;
   std::vector<uint64_t> rows;
+  int id = 0;  // kind 4: the launch's entry in the call's list of coefficient sets
 };
 
 static PtrLaunch& ptr_launch_of(std::vector<PtrLaunch>& launches, int kind, int nob, uint32_t rs) {
@@ -1964,6 +1966,137 @@ int cec_update_batch(cec_codec* c, const uint8_t* d_old, const uint8_t* d_new, u
                   shard_len, shard_len, slots.data(), coef.data(), (int)slots.size(), c->m, true,
                   nseg, pick_stream(c, hip_stream));
   return check_launch();
+}
+
+// cec_encode_idx_ptrs (in_b == NULL) and cec_update_ptrs (in_a the old bytes, in_b the new ones).
+// Segments are grouped by their (input set, parity set), as reconstruct_ptrs_impl groups by
+// pattern; a group's work is cut into output chunks of kRtMaxOut and input chunks of kAccMaxIn
+// (chunks after the first accumulate: stream order), one launch each over the group's rows {the
+// chunk's inputs [, their new bytes], the chunk's parities}. A launch's coefficients travel in its
+// kernel arguments, so launches are never merged across groups.
+static int acc_ptrs_impl(cec_codec* c, const uint8_t* const* in_a, const uint8_t* const* in_b,
+                         uint8_t* const* parity, size_t nseg, size_t shard_len, bool accumulate,
+                         void* hip_stream) {
+  const int k = c->k, m = c->m;
+  const bool upd = in_b != nullptr;
+  if (upd)
+    for (size_t i = 0; i < nseg * (size_t)k; ++i)
+      if (!in_a[i] != !in_b[i])
+        return set_err(CEC_EINVAL, "a data slot has one of its old and new bytes");
+  struct Group {
+    std::vector<int> ins, outs;
+    std::vector<uint32_t> segs;
+  };
+  std::unordered_map<std::string, size_t> gidx;
+  std::vector<Group> groups;
+  std::string key((size_t)k + m, '\0');
+  uintptr_t bits = 0;  // OR of every address read or written: the alignment of the call
+  std::unordered_set<uintptr_t> pars;  // every parity address the call writes
+  std::vector<uint8_t*> zeros;         // overwrite mode: named parity of segments that feed nothing
+  for (size_t s = 0; s < nseg; ++s) {
+    const uint8_t* const* dp = in_a + s * k;
+    uint8_t* const* pp = parity + s * m;
+    int nin = 0, nout = 0;
+    for (int j = 0; j < k; ++j) nin += key[j] = dp[j] ? 1 : 0;
+    for (int o = 0; o < m; ++o) nout += key[k + o] = pp[o] ? 1 : 0;
+    if (!nout || (!nin && accumulate)) continue;  // no row, no work, pointers not looked at
+    for (int o = 0; o < m; ++o) {
+      if (!pp[o]) continue;
+      if (!pars.insert((uintptr_t)pp[o]).second)
+        return set_err(CEC_EINVAL, "a parity shard is named twice");
+      if (nin) bits |= (uintptr_t)pp[o];
+      else zeros.push_back(pp[o]);  // the encode of nothing
+    }
+    if (!nin) continue;
+    auto it = gidx.find(key);
+    if (it == gidx.end()) {
+      it = gidx.emplace(key, groups.size()).first;
+      groups.emplace_back();
+      Group& g = groups.back();
+      for (int j = 0; j < k; ++j)
+        if (key[j]) g.ins.push_back(j);
+      for (int o = 0; o < m; ++o)
+        if (key[k + o]) g.outs.push_back(o);
+    }
+    groups[it->second].segs.push_back((uint32_t)s);
+  }
+  for (const Group& g : groups)  // inputs may repeat (they are only read), but none is a parity
+    for (uint32_t s : g.segs)
+      for (int j : g.ins) {
+        const uintptr_t a = (uintptr_t)in_a[(size_t)s * k + j];
+        const uintptr_t b = upd ? (uintptr_t)in_b[(size_t)s * k + j] : a;
+        if (pars.count(a) || pars.count(b))
+          return set_err(CEC_EINVAL, "a parity shard is an input of the call");
+        bits |= a | b;
+      }
+  if (groups.empty() && zeros.empty()) return CEC_OK;
+  const bool vec_ok = (bits & 15) == 0;
+  struct Coefs {
+    int nin, nout;
+    bool accumulate;
+    std::vector<uint8_t> coef;  // [nin][nout]
+  };
+  std::vector<Coefs> coefs;
+  std::vector<PtrLaunch> launches;
+  for (const Group& g : groups) {
+    const int nin = (int)g.ins.size(), nout = (int)g.outs.size();
+    for (int o0 = 0; o0 < nout; o0 += cec::kRtMaxOut) {
+      const int no = std::min(nout - o0, cec::kRtMaxOut);
+      for (int j0 = 0; j0 < nin; j0 += cec::kAccMaxIn) {
+        const int ni = std::min(nin - j0, cec::kAccMaxIn);
+        Coefs cf{ni, no, accumulate || j0 > 0, std::vector<uint8_t>((size_t)ni * no)};
+        for (int j = 0; j < ni; ++j)
+          for (int o = 0; o < no; ++o)
+            cf.coef[(size_t)j * no + o] = c->E->v[k + g.outs[o0 + o]][g.ins[j0 + j]];
+        PtrLaunch l{4, cec::rt_bucket(no), (uint32_t)((upd ? 2 : 1) * ni + no), {},
+                    (int)coefs.size()};
+        l.rows.reserve(g.segs.size() * l.rs);
+        for (uint32_t s : g.segs) {
+          for (int j = 0; j < ni; ++j)
+            l.rows.push_back((uint64_t)(uintptr_t)in_a[(size_t)s * k + g.ins[j0 + j]]);
+          if (upd)
+            for (int j = 0; j < ni; ++j)
+              l.rows.push_back((uint64_t)(uintptr_t)in_b[(size_t)s * k + g.ins[j0 + j]]);
+          for (int o = 0; o < no; ++o)
+            l.rows.push_back((uint64_t)(uintptr_t)parity[(size_t)s * m + g.outs[o0 + o]]);
+        }
+        coefs.push_back(std::move(cf));
+        launches.push_back(std::move(l));
+      }
+    }
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, hip_stream);
+  Uploads up{c->stream, c->arena};
+  int rc = run_ptr_table(c, launches, up, st, [] { return (int)CEC_OK; },
+                         [&](const PtrLaunch& l, const uint64_t* tab, uint32_t nrows) {
+                           const Coefs& cf = coefs[l.id];
+                           cec::launch_acc_ptrs(tab, nrows, cf.coef.data(), cf.nin, cf.nout, upd,
+                                                cf.accumulate, shard_len, vec_ok, st);
+                         });
+  for (uint8_t* z : zeros) {
+    if (rc) break;
+    const hipError_t e = hipMemsetAsync(z, 0, shard_len, st);
+    if (e != hipSuccess)
+      rc = set_err(CEC_EHIP, std::string("encode_idx: ") + hipGetErrorString(e));
+  }
+  return rc;
+}
+
+int cec_encode_idx_ptrs(cec_codec* c, const uint8_t* const* data, uint8_t* const* parity,
+                        size_t nseg, size_t shard_len, int accumulate, void* hip_stream) {
+  if (!c || (nseg && (!data || !parity))) return set_err(CEC_EINVAL, "null");
+  if (int rc = check_acc_shape(nseg, shard_len)) return rc;
+  if (nseg == 0) return CEC_OK;
+  return acc_ptrs_impl(c, data, nullptr, parity, nseg, shard_len, accumulate != 0, hip_stream);
+}
+
+int cec_update_ptrs(cec_codec* c, const uint8_t* const* old_data, const uint8_t* const* new_data,
+                    uint8_t* const* parity, size_t nseg, size_t shard_len, void* hip_stream) {
+  if (!c || (nseg && (!old_data || !new_data || !parity))) return set_err(CEC_EINVAL, "null");
+  if (int rc = check_acc_shape(nseg, shard_len)) return rc;
+  if (nseg == 0) return CEC_OK;
+  return acc_ptrs_impl(c, old_data, new_data, parity, nseg, shard_len, true, hip_stream);
 }
 
 int cec_sha256_batch(cec_codec* c, const uint8_t* d_data, const uint8_t* d_parity, size_t nseg,

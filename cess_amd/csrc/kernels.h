@@ -238,6 +238,14 @@ void launch_acc(const uint8_t* in_a, const uint8_t* in_b, uint64_t in_seg_stride
                 uint64_t par_shard_stride, uint64_t len, const uint32_t* slots,
                 const uint8_t* coef, int nin, int nout, bool accumulate, uint64_t nseg,
                 hipStream_t st);
+// The same product on scattered shards (cec_encode_idx_ptrs, cec_update_ptrs): row r of the device
+// table `tab` is {nin input addresses, with `update` the nin addresses of their new bytes, nout
+// parity addresses}, (update ? 2 : 1) * nin + nout words, each address `len` bytes. One launch
+// (per 65535 rows): nin <= kAccMaxIn, nout <= kRtMaxOut (the caller cuts the chunks; nothing is
+// launched otherwise), coef[j * nout + o] copied into the kernel arguments. vec_ok: every address
+// of the table is 16-byte aligned (16-byte columns and a byte tail; else byte-wise).
+void launch_acc_ptrs(const uint64_t* tab, uint32_t nrows, const uint8_t* coef, int nin, int nout,
+                     bool update, bool accumulate, uint64_t len, bool vec_ok, hipStream_t st);
 
 // ok[s] = 0 for every segment s whose seg_bytes of a and b differ (ok preset by the caller).
 void launch_cmp_segments(const uint8_t* a, const uint8_t* b, uint64_t seg_bytes, uint64_t nseg,

@@ -745,7 +745,6 @@ __global__ __launch_bounds__(256) void k_ct_bytes(Layout L, const uint32_t* __re
 // Program chunks are read through the constant address space: they are never written while a
 // kernel runs, so uniform-address loads become s_load (SGPR results, SALU mask expansion).
 typedef const uint32_t __attribute__((address_space(4))) cu32;
-typedef const uint64_t __attribute__((address_space(4))) cu64;
 __device__ __forceinline__ const cu32* as_const(const uint32_t* p) {
   return (const cu32*)(uintptr_t)p;
 }
@@ -755,15 +754,8 @@ __device__ __forceinline__ const uint32_t* as_const_ptr(const uint32_t* const* a
 }
 
 // Pointer-table rows (see "Pointer-table addressing" below) are read through the constant address
-// space too, and their words are turned into address_space(1) pointers, not generic ones: the
-// accesses stay global_load / global_store (a flat access counts on lgkmcnt too and would
-// serialise with the scalar reads, see shard_ptr_sel).
-typedef uint8_t __attribute__((address_space(1))) gu8;
-
-__device__ __forceinline__ const cu64* tab_row(const uint64_t* tab, uint64_t row, uint32_t rs) {
-  return (const cu64*)(uintptr_t)tab + row * rs;
-}
-__device__ __forceinline__ gu8* gptr(uint64_t a) { return (gu8*)a; }
+// space too, and their words are turned into address_space(1) pointers, not generic ones (cu64,
+// gu8, tab_row and gptr of dev_util.h; see shard_ptr_sel for what a flat access would cost).
 
 template <bool NT, class TV>
 __device__ __forceinline__ TV gld(const gu8* p) {

@@ -574,6 +574,110 @@ class Encoder:
         check(self._lib.cec_xor_ptrs(self._h, d, a, nrows, nsrc, size,
                                      self._device_stream(stream)), "XorDevice")
 
+    def EncodeIdxDevice(self, dataShard, idx: int, parity: Sequence, accumulate: bool = True,
+                        stream=None) -> None:
+        """klauspost EncodeIdx on one segment's scattered device tensors (cec_encode_idx_ptrs):
+        parity[o] ^= E[k+o][idx] * dataShard for every parity tensor held here. `parity` is a list
+        of m 1-D uint8 device tensors or None (None: that parity shard is not held here; it is
+        neither read nor written). accumulate=False overwrites the parity without reading it.
+        Enqueued on `stream` (default: torch's current stream) and not waited for."""
+        if not 0 <= idx < self.DataShards:
+            raise ErrInvShardNum(ErrInvShardNum.__doc__)
+        if len(parity) != self.ParityShards:
+            raise ErrTooFewShards(ErrTooFewShards.__doc__)
+        if dataShard is None:
+            raise ErrShardNoData(ErrShardNoData.__doc__)
+        data = [None] * self.DataShards
+        data[idx] = dataShard
+        self.EncodeIdxDeviceBatch([data], [parity], accumulate, stream)
+
+    def EncodeIdxDeviceBatch(self, data: Sequence, parity: Sequence, accumulate: bool = True,
+                             stream=None) -> None:
+        """EncodeIdxDevice for many segments in one call, each with its own fed set and its own
+        parity set: `data[s]` is a list of k 1-D uint8 device tensors or None (a None entry, or
+        None for the list: not fed in this call), `parity[s]` a list of m tensors or None (not
+        held here). Every named parity receives the contributions of its segment's fed shards.
+        With accumulate=False a named parity of a segment that feeds nothing is zeroed (the encode
+        of nothing), with accumulate=True it is left as it is. Every tensor must be contiguous,
+        of one length and on the codec's GPU (TypeError otherwise)."""
+        nseg = len(data)
+        if len(parity) != nseg:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        self._acc_device(data, None, parity, accumulate, stream, "EncodeIdxDevice")
+
+    def UpdateDevice(self, shards: Sequence, newDatashards: Sequence, stream=None) -> None:
+        """klauspost Update on one segment's scattered device tensors (cec_update_ptrs): `shards`
+        is the encoded segment (k + m 1-D uint8 device tensors; an unchanged data shard may be
+        None, and so may a parity shard that is not held here), `newDatashards` the k data shards
+        with None for unchanged ones. The held parity tensors are brought up to date in place from
+        the old and new bytes of the changed shards; no data tensor is written. Enqueued on
+        `stream` (default: torch's current stream) and not waited for."""
+        k = self.DataShards
+        if len(shards) != self.Shards or len(newDatashards) != k:
+            raise ErrTooFewShards(ErrTooFewShards.__doc__)
+        self._check_device_shards([t for t in list(shards) + list(newDatashards)
+                                   if t is not None])
+        self.UpdateDeviceBatch([shards[:k]], [newDatashards], [shards[k:]], stream)
+
+    def UpdateDeviceBatch(self, olds: Sequence, news: Sequence, parities: Sequence,
+                          stream=None) -> None:
+        """UpdateDevice for many segments in one call, each with its own changed set and its own
+        parity set: `olds[s]` and `news[s]` are lists of k tensors or None, `parities[s]` a list
+        of m tensors or None (None: not held here). A slot with a new tensor is changed and needs
+        its old one (ErrInvalidInput otherwise); an old tensor without a new one is unchanged and
+        not read. Every tensor must be contiguous, of one length and on the codec's GPU (TypeError
+        otherwise)."""
+        nseg = len(olds)
+        if len(news) != nseg or len(parities) != nseg:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        self._acc_device(olds, news, parities, True, stream, "UpdateDevice")
+
+    def _acc_device(self, olds, news, parities, accumulate, stream, what) -> None:
+        """EncodeIdxDeviceBatch (news None: olds are the fed shards) and UpdateDeviceBatch."""
+        nseg, k, m = len(olds), self.DataShards, self.ParityShards
+        ins, outs, used = [], [], []
+        for s in range(nseg):
+            old = olds[s] if olds[s] is not None else [None] * k
+            par = parities[s] if parities[s] is not None else [None] * m
+            new = old if news is None else (news[s] if news[s] is not None else [None] * k)
+            if len(old) != k or len(new) != k or len(par) != m:
+                raise ErrTooFewShards(ErrTooFewShards.__doc__)
+            row = []
+            for j in range(k):
+                if new[j] is None:
+                    continue
+                if old[j] is None:
+                    raise ErrInvalidInput(ErrInvalidInput.__doc__)
+                row.append((s * k + j, old[j], new[j]))
+                used += [old[j]] if news is None else [old[j], new[j]]
+            ins.append(row)
+            outs.append([(s * m + o, t) for o, t in enumerate(par) if t is not None])
+            used += [t for _, t in outs[-1]]
+        if not used:
+            return
+        size = self._check_device_shards(used)
+        work = [s for s in range(nseg) if outs[s] and (ins[s] or not accumulate)]
+        if not work:  # nothing fed or changed, or no parity held: no C call
+            return
+        import torch
+        dev = torch.device("cuda", self.device)
+        if any(t.device != dev for t in used):  # (_dev_ptr refuses host and strided tensors)
+            raise TypeError("device shards must live on the codec's GPU")
+        a = (c_void_p * (nseg * k))()
+        b = (c_void_p * (nseg * k))()
+        p = (c_void_p * (nseg * m))()
+        for s in work:
+            for i, t_old, t_new in ins[s]:
+                a[i], b[i] = _dev_ptr(t_old), _dev_ptr(t_new)
+            for i, t in outs[s]:
+                p[i] = _dev_ptr(t)
+        st = self._device_stream(stream)
+        if news is None:
+            check(self._lib.cec_encode_idx_ptrs(self._h, a, p, nseg, size,
+                                                1 if accumulate else 0, st), what)
+        else:
+            check(self._lib.cec_update_ptrs(self._h, a, b, p, nseg, size, st), what)
+
     def _check_device_shards(self, tensors) -> int:
         import torch
         size = 0

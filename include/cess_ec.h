@@ -92,7 +92,7 @@ int cec_verify(cec_codec* codec, uint8_t* const* shards, size_t shard_len, int* 
  * a decode program from the codec's cache, which may evict it while a graph still points at it:
  * do not capture those, nor cec_reconstruct_some_batch, nor the pointer-table calls
  * (cec_reconstruct_ptrs, cec_encode_ptrs, cec_verify_ptrs, cec_reconstruct_partial_ptrs,
- * cec_xor_ptrs: their kernels read a codec-owned table that is retired once the call's launches
+ * cec_xor_ptrs, cec_encode_idx_ptrs, cec_update_ptrs: their kernels read a codec-owned table that is retired once the call's launches
  * complete). A single 16 MiB RS(2,1) segment's
  * encode + three rebuilds: 29.5 us eagerly, 24.8 us as one graph (profiles/r05/graph_probe.log). */
 int cec_encode_batch(cec_codec* codec, const uint8_t* d_data, uint8_t* d_parity, size_t nseg,
@@ -300,6 +300,49 @@ int cec_encode_idx_batch(cec_codec* codec, const uint8_t* d_shard, size_t shard_
  * ([nseg][m][shard_len]) is updated in place. */
 int cec_update_batch(cec_codec* codec, const uint8_t* d_old, const uint8_t* d_new, uint8_t* d_parity,
                      size_t nseg, size_t shard_len, const uint8_t* changed, void* hip_stream);
+/* EncodeIdx and Update on scattered shards, in place: the two calls above without the batch.
+ * data, old_data, new_data: HOST arrays of nseg*k DEVICE pointers; parity: a HOST array of nseg*m
+ * DEVICE pointers, each shard_len bytes. Every segment has its own fed (or changed) set and its own
+ * parity set, all in one call.
+ *  - cec_encode_idx_ptrs: data[s*k+j] non-NULL = data shard j of segment s is fed in this call;
+ *    parity[s*m+o] non-NULL = parity shard o of segment s is held here at that address (a NULL one
+ *    is neither read nor written: under a placement that spreads a segment's parity over GPUs each
+ *    names its own). Every named parity receives
+ *      parity[o] ^= XOR over the fed j of E[k+o][j] * data_j.
+ *    accumulate == 0: parity[o] = that sum, the old parity not read; a segment with a named parity
+ *    and no fed shard gets that parity zero-filled (the encode of nothing, the neutral element, as
+ *    in cec_reconstruct_partial_ptrs). accumulate != 0: such a segment is not touched.
+ *  - cec_update_ptrs: a data slot with old_data[s*k+j] and new_data[s*k+j] both non-NULL is
+ *    changed, both NULL unchanged. Every named parity receives
+ *      parity[o] ^= XOR over the changed j of E[k+o][j] * (old_j ^ new_j).
+ *    Only parity is written; the caller swaps in the new data. old == new for a slot is legal and
+ *    contributes zero.
+ *  - Reads: the fed or changed shards of segments that do work, and with accumulate (always for
+ *    Update) their named parity. Writes: nothing but the shard_len bytes at each named parity of
+ *    those segments. A segment without a fed or changed slot, or without a named parity, gets no
+ *    workgroup and its pointers are not looked at further (but for the zero fill above).
+ *  - Validation: everything is validated before anything is enqueued; on an error no byte is
+ *    written. CEC_EINVAL: a NULL codec; a NULL array with nseg > 0; a slot with exactly one of its
+ *    old and new entries (the arrays are out of step); the same parity address twice in the call
+ *    (two rows would race on it); a parity address equal to any input address of the call. Equal
+ *    addresses are what is checked: partial overlaps are the caller's duty, as in cec_xor_ptrs.
+ *    Input addresses may repeat within and across segments: they are only read. CEC_ESHARDLEN:
+ *    shard_len == 0; the shard_len bound of the batch forms applies. nseg == 0: CEC_OK.
+ *  - Pointer arrays: they belong to the caller again on return. The device table comes from the
+ *    codec's pool and is retired once the launches complete, as in cec_reconstruct_ptrs; the work
+ *    is enqueued on hip_stream and not waited for.
+ *  - Alignment: any alignment and any shard_len >= 1 is correct. When every address read or
+ *    written is 16-byte aligned the kernels take 16-byte columns with a byte tail, otherwise the
+ *    whole call runs byte-wise (the fallback is per call).
+ *  - HIP graph capture: not capturable: the kernels read the codec-owned table.
+ * No decode program is involved and nothing enters the LRU cache: segments are grouped by their
+ * (input set, parity set), and every group runs one launch per chunk of 32 parities and 8 inputs,
+ * its coefficients in the kernel arguments as in the batch forms. */
+int cec_encode_idx_ptrs(cec_codec* codec, const uint8_t* const* data, uint8_t* const* parity,
+                        size_t nseg, size_t shard_len, int accumulate, void* hip_stream);
+int cec_update_ptrs(cec_codec* codec, const uint8_t* const* old_data,
+                    const uint8_t* const* new_data, uint8_t* const* parity, size_t nseg,
+                    size_t shard_len, void* hip_stream);
 /* Host-buffer forms (klauspost-shaped, staged through HBM, synchronous). Only what is read is
  * staged: the shard and the m parity shards, or the old and new bytes of the changed shards and the
  * parity; the parity is copied back.

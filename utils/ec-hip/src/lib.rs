@@ -192,6 +192,12 @@ pub mod sys {
         pub fn cec_update_batch(c: *mut cec_codec, d_old: *const u8, d_new: *const u8,
                                 d_parity: *mut u8, nseg: usize, shard_len: usize,
                                 changed: *const u8, stream: *mut c_void) -> c_int;
+        pub fn cec_encode_idx_ptrs(c: *mut cec_codec, data: *const *const u8,
+                                   parity: *const *mut u8, nseg: usize, shard_len: usize,
+                                   accumulate: c_int, stream: *mut c_void) -> c_int;
+        pub fn cec_update_ptrs(c: *mut cec_codec, old_data: *const *const u8,
+                               new_data: *const *const u8, parity: *const *mut u8, nseg: usize,
+                               shard_len: usize, stream: *mut c_void) -> c_int;
         pub fn cec_encode_idx(c: *mut cec_codec, data_shard: *const u8, idx: c_int,
                               parity: *const *mut u8, shard_len: usize) -> c_int;
         pub fn cec_update(c: *mut cec_codec, shards: *const *mut u8,
@@ -612,6 +618,47 @@ impl ReedSolomon {
             return Err(Error::from_code(CEC_EINVAL));
         }
         check(cec_xor_ptrs(self.c, dst.as_ptr(), src.as_ptr(), dst.len(), nsrc, len, stream))
+    }
+
+    /// EncodeIdx on scattered device shards in place (`cec_encode_idx_ptrs`): `data` holds
+    /// `nseg * k` entries and `parity` `nseg * m`, segment by segment. A non-null `data` entry is a
+    /// data shard fed in this call, a non-null `parity` entry a parity shard held here; every
+    /// named parity o of a segment receives XOR over its fed shards j of E[k+o][j] * data_j
+    /// (`accumulate`: is XORed with it; otherwise overwritten, zero-filled where nothing is fed).
+    /// Enqueued on `stream` and not waited for; the slices may be reused as soon as the call
+    /// returns.
+    ///
+    /// # Safety
+    /// Every non-null address must be device memory of `shard_len` bytes on the codec's GPU that
+    /// stays valid until the stream has passed the call's work; parity shards must not overlap
+    /// each other or a fed shard.
+    pub unsafe fn encode_idx_device(&self, data: &[*const u8], parity: &[*mut u8],
+                                    shard_len: usize, accumulate: bool,
+                                    stream: *mut c_void) -> Result<(), Error> {
+        if data.len() % self.k != 0 || parity.len() != data.len() / self.k * self.m {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        check(cec_encode_idx_ptrs(self.c, data.as_ptr(), parity.as_ptr(), data.len() / self.k,
+                                  shard_len, accumulate as c_int, stream))
+    }
+
+    /// Update on scattered device shards in place (`cec_update_ptrs`): `old_data` and `new_data`
+    /// hold `nseg * k` entries and `parity` `nseg * m`. A slot with both entries non-null is
+    /// changed (both null: unchanged); every named parity o of a segment is XORed with the sum
+    /// over its changed slots j of E[k+o][j] * (old_j ^ new_j). Only parity is written. Enqueued
+    /// on `stream` and not waited for; the slices may be reused as soon as the call returns.
+    ///
+    /// # Safety
+    /// As `encode_idx_device`, for the old and the new bytes alike.
+    pub unsafe fn update_device(&self, old_data: &[*const u8], new_data: &[*const u8],
+                                parity: &[*mut u8], shard_len: usize,
+                                stream: *mut c_void) -> Result<(), Error> {
+        if old_data.len() != new_data.len() || old_data.len() % self.k != 0
+            || parity.len() != old_data.len() / self.k * self.m {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        check(cec_update_ptrs(self.c, old_data.as_ptr(), new_data.as_ptr(), parity.as_ptr(),
+                              old_data.len() / self.k, shard_len, stream))
     }
 
     /// The decode rows of the `required` lost shards of pattern `present` (`cec_decode_rows`):
