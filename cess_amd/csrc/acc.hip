@@ -205,20 +205,12 @@ __global__ __launch_bounds__(256) void k_acc(AccArgs a) {
   acc_fold<NOB, 1, UPD, uint32_t>(K, a.nin, a.nout, accumulate, ld_in, ld_par, st_par);
 }
 
-constexpr uint32_t kMaxGridY = 65535;
-
-template <class F>
-void for_y_slices(uint64_t nseg, F f) {
-  for (uint64_t s0 = 0; s0 < nseg; s0 += kMaxGridY)
-    f((uint32_t)s0, (uint32_t)(nseg - s0 < kMaxGridY ? nseg - s0 : kMaxGridY));
-}
-
 template <int NOB, bool UPD>
 void run_acc(AccArgs a, uint64_t nseg, hipStream_t st) {
   constexpr int U = 1;
   uint64_t gx = (a.flags & kAccVec16) ? (a.len / 16 + 256 * U - 1) / (256 * U) : (a.len + 255) / 256;
   if (gx == 0) gx = 1;  // tail-only shard
-  for_y_slices(nseg, [&](uint32_t s0, uint32_t ny) {
+  for_y_chunks(nseg, [&](uint32_t s0, uint32_t ny) {
     a.seg0 = s0;
     hipLaunchKernelGGL((k_acc<NOB, U, UPD>), dim3((unsigned)gx, ny), dim3(256), 0, st, a);
   });
@@ -314,7 +306,7 @@ void run_acc_ptrs(AccPtrArgs a, uint64_t nrows, hipStream_t st) {
   constexpr int U = 1;
   uint64_t gx = (a.flags & kAccVec16) ? (a.len / 16 + 256 * U - 1) / (256 * U) : (a.len + 255) / 256;
   if (gx == 0) gx = 1;  // tail-only shard
-  for_y_slices(nrows, [&](uint32_t r0, uint32_t ny) {
+  for_y_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
     a.row0 = r0;
     hipLaunchKernelGGL((k_acc_ptrs<NOB, U, UPD>), dim3((unsigned)gx, ny), dim3(256), 0, st, a);
   });

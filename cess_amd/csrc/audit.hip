@@ -45,15 +45,14 @@ void launch_chunk_gather(const Layout& L, int nshards, uint64_t nfrag, const uin
   const bool v16 = (bits & 15) == 0;
   const uint64_t per_tile = v16 ? 256 * 16 : 256;
   const uint32_t tiles = (uint32_t)((chunk_len + per_tile - 1) / per_tile);
-  for (uint64_t f0 = 0; f0 < nfrag; f0 += 65535) {
-    const uint32_t ny = (uint32_t)(nfrag - f0 < 65535 ? nfrag - f0 : 65535);
+  for_y_chunks(nfrag, [&](uint32_t f0, uint32_t ny) {
     if (v16)
       hipLaunchKernelGGL(k_chunk_gather<true>, dim3(tiles * nidx, ny), dim3(256), 0, st, L,
-                         nshards, d_idx, nidx, chunk_len, tiles, (uint32_t)f0, out);
+                         nshards, d_idx, nidx, chunk_len, tiles, f0, out);
     else
       hipLaunchKernelGGL(k_chunk_gather<false>, dim3(tiles * nidx, ny), dim3(256), 0, st, L,
-                         nshards, d_idx, nidx, chunk_len, tiles, (uint32_t)f0, out);
-  }
+                         nshards, d_idx, nidx, chunk_len, tiles, f0, out);
+  });
 }
 
 }  // namespace cec

@@ -1438,20 +1438,62 @@ int cec_decode_rows(int k, int m, const uint8_t* present, const uint8_t* require
 // retired in stream order behind them.
 
 // One kernel launch of such a call and its rows of the table.
+enum class PtrKind {
+  rs21,      // RS(2,1), compile-time coefficients
+  bitplane,  // run-time program, the bit-plane product where the bucket has one (k_rtb's cases)
+  masks,     // run-time program, the per-bit mask product
+  xor_rows,  // cec_xor_ptrs
+  acc        // parity accumulation (acc_ptrs_impl; never merged: see id)
+};
 struct PtrLaunch {
-  int kind;  // 0: RS(2,1) compile-time, 1: bit-plane (k_rtb's cases), 2: general, 3: cec_xor_ptrs,
-             // 4: parity accumulation (acc_ptrs_impl; never merged: see id)
+  PtrKind kind;
   int nob;
   uint32_t rs;
   std::vector<uint64_t> rows;
-  int id = 0;  // kind 4: the launch's entry in the call's list of coefficient sets
+  int id = 0;  // acc: the launch's entry in the call's list of coefficient sets
 };
 
-static PtrLaunch& ptr_launch_of(std::vector<PtrLaunch>& launches, int kind, int nob, uint32_t rs) {
+static PtrLaunch& ptr_launch_of(std::vector<PtrLaunch>& launches, PtrKind kind, int nob,
+                                uint32_t rs) {
   for (auto& l : launches)
     if (l.kind == kind && l.nob == nob && l.rs == rs) return l;
   launches.push_back({kind, nob, rs, {}});
   return launches.back();
+}
+
+// The kernel of an rs21 / bitplane / masks launch over its `nrows` rows at `tab`, with what `sink`
+// does at the rows' output positions (`d_ok`: the compare's flags).
+static void launch_ptr_rows(const PtrLaunch& l, cec::PtrSink sink, const uint64_t* tab,
+                            uint32_t nrows, size_t shard_len, bool vec_ok, uint8_t* d_ok,
+                            hipStream_t st) {
+  if (l.kind == PtrKind::rs21)
+    cec::launch_ptrs_rs21(sink, tab, nrows, shard_len, vec_ok, d_ok, st);
+  else
+    cec::launch_ptrs_rt(sink, l.kind == PtrKind::bitplane, tab, nrows, l.rs, l.nob, shard_len,
+                        vec_ok, d_ok, st);
+}
+
+// Segments of a call grouped by a key string: the index of the key's group among the call's
+// `ngroups` groups, or ngroups for a key not seen before, whose group the caller then appends.
+static size_t group_of(std::unordered_map<std::string, size_t>& gidx, const std::string& key,
+                       size_t ngroups) {
+  const auto it = gidx.find(key);
+  return it != gidx.end() ? it->second : gidx.emplace(key, ngroups).first->second;
+}
+
+// The RS(2,1) rows {input 0, input 1, output, case} of program p (one lost shard: p.single) for
+// the segments `segs`; with `seg_word` the segment index rides in the case word's high half.
+static void add_rs21_rows(const cec_codec* c, std::vector<PtrLaunch>& launches, const Program& p,
+                          const std::vector<uint32_t>& segs, const uint8_t* const* src,
+                          uint8_t* const* dst, bool seg_word) {
+  const int n = c->k + c->m;
+  PtrLaunch& l = ptr_launch_of(launches, PtrKind::rs21, 1, 4);
+  for (uint32_t s : segs) {
+    l.rows.push_back((uint64_t)(uintptr_t)src[(size_t)s * n + p.in_idx[0]]);
+    l.rows.push_back((uint64_t)(uintptr_t)src[(size_t)s * n + p.in_idx[1]]);
+    l.rows.push_back((uint64_t)(uintptr_t)dst[(size_t)s * n + p.out_idx[0]]);
+    l.rows.push_back((uint64_t)p.out_idx[0] | (seg_word ? (uint64_t)s << 32 : 0));
+  }
 }
 
 // The run-time rows of program p for the segments `segs`: per chunk and segment one row {program
@@ -1465,8 +1507,8 @@ static void add_rt_rows(const cec_codec* c, std::vector<PtrLaunch>& launches, co
   int o0 = 0;
   for (const RtChunk& ch : p.chunks) {
     const bool rtb = cec::rt_takes_rtb(c->opts, ch.nob, ch.nin);  // as launch_chunk
-    PtrLaunch& l = ptr_launch_of(launches, rtb && ch.nob <= 4 ? 1 : 2, ch.nob,
-                                 (uint32_t)(1 + ch.nin + ch.nob + (seg_word ? 1 : 0)));
+    PtrLaunch& l = ptr_launch_of(launches, rtb && ch.nob <= 4 ? PtrKind::bitplane : PtrKind::masks,
+                                 ch.nob, (uint32_t)(1 + ch.nin + ch.nob + (seg_word ? 1 : 0)));
     for (uint32_t s : segs) {
       const size_t r0 = l.rows.size();
       l.rows.resize(r0 + l.rs, 0);
@@ -1521,10 +1563,22 @@ static int run_ptr_table(cec_codec* c, const std::vector<PtrLaunch>& launches, U
   return rc ? rc : mrc;
 }
 
+// Behind the launches of call `what` (rc: their code, kept when set): clear the shard_len bytes at
+// every address of `zeros`, the outputs whose product is of nothing.
+static int clear_shards(int rc, const std::vector<uint8_t*>& zeros, size_t shard_len,
+                        hipStream_t st, const char* what) {
+  for (uint8_t* z : zeros) {
+    if (rc) break;
+    const hipError_t e = hipMemsetAsync(z, 0, shard_len, st);
+    if (e != hipSuccess) rc = set_err(CEC_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+  }
+  return rc;
+}
+
 // cec_reconstruct_ptrs, cec_encode_ptrs and, with `d_ok`, cec_verify_ptrs. There `dst` names
-// expectations: the same programs and rows, run by the compare forms of the kernels, which read
-// what dst names and write only d_ok (preset to 1 here, behind the validation). Their rows also
-// hold the segment index, see launch_vptrs_*.
+// expectations: the same programs and rows, run with PtrSink::compare, which reads what dst names
+// and writes only d_ok (preset to 1 here, behind the validation). Their rows also hold the segment
+// index, see kernels.h.
 static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_t* const* dst,
                                  size_t nseg, size_t shard_len, hipStream_t st,
                                  uint8_t* d_ok = nullptr) {
@@ -1547,16 +1601,14 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
       key[i] = sp[i] ? 1 : 0;
       key[n + i] = !sp[i] && dp[i] ? 1 : 0;
     }
-    auto it = gidx.find(key);
-    if (it == gidx.end()) {
+    const size_t gi = group_of(gidx, key, groups.size());
+    if (gi == groups.size()) {
       const uint8_t* f = reinterpret_cast<const uint8_t*>(key.data());
       ProgPtr p;
-      int rc = get_decode(c, f, false, &p, &up.arena, f + n);
-      if (rc) return rc;
-      it = gidx.emplace(key, groups.size()).first;
+      if (int rc = get_decode(c, f, false, &p, &up.arena, f + n)) return rc;
       groups.push_back({p, {}});
     }
-    Group& g = groups[it->second];
+    Group& g = groups[gi];
     const Program& p = *g.prog;
     if (!p.nout) continue;  // nothing wanted: no row, no work
     for (int o = 0; o < p.nout; ++o) {
@@ -1574,37 +1626,14 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
   // launches: RS(2,1) rows for the compile-time kernel; otherwise one launch per (kernel, bucket)
   // over the rows of every pattern's chunk of that kind
   std::vector<PtrLaunch> launches;
-  // one launch's kernel: the store forms (rebuild, encode) or the compare forms (verify)
-  auto launch_store = [&](const PtrLaunch& l, const uint64_t* tab, uint32_t nrows) {
-    if (l.kind == 0)
-      cec::launch_ptrs_rs21(tab, nrows, shard_len, vec_ok, st);
-    else if (l.kind != 1 || !cec::launch_ptrs_rtb(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st))
-      cec::launch_ptrs_rt(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st);
-  };
-  auto launch_compare = [&](const PtrLaunch& l, const uint64_t* tab, uint32_t nrows) {
-    if (l.kind == 0)
-      cec::launch_vptrs_rs21(tab, nrows, shard_len, vec_ok, d_ok, st);
-    else if (l.kind != 1 ||
-             !cec::launch_vptrs_rtb(tab, nrows, l.rs, l.nob, shard_len, vec_ok, d_ok, st))
-      cec::launch_vptrs_rt(tab, nrows, l.rs, l.nob, shard_len, vec_ok, d_ok, st);
-  };
   const bool ct21 = k == 2 && c->m == 1 && !c->force_generic;
   bool any_rows = false;
   for (const Group& g : groups) {
     const Program& p = *g.prog;
     if (!p.nout || g.segs.empty()) continue;
     any_rows = true;
-    if (ct21) {  // one lost shard: p.single
-      PtrLaunch& l = ptr_launch_of(launches, 0, 1, 4);
-      for (uint32_t s : g.segs) {
-        l.rows.push_back((uint64_t)(uintptr_t)src[(size_t)s * n + p.in_idx[0]]);
-        l.rows.push_back((uint64_t)(uintptr_t)src[(size_t)s * n + p.in_idx[1]]);
-        l.rows.push_back((uint64_t)(uintptr_t)dst[(size_t)s * n + p.out_idx[0]]);
-        l.rows.push_back((uint64_t)p.out_idx[0] | (d_ok ? (uint64_t)s << 32 : 0));
-      }
-      continue;
-    }
-    add_rt_rows(c, launches, p, g.segs, src, dst, d_ok != nullptr);
+    if (ct21) add_rs21_rows(c, launches, p, g.segs, src, dst, d_ok != nullptr);
+    else add_rt_rows(c, launches, p, g.segs, src, dst, d_ok != nullptr);
   }
   auto preset_ok = [&]() -> int {
     if (!d_ok) return CEC_OK;
@@ -1616,8 +1645,8 @@ static int reconstruct_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_
   if (any_rows)
     rc = run_ptr_table(c, launches, up, st, preset_ok,
                        [&](const PtrLaunch& l, const uint64_t* tab, uint32_t nrows) {
-                         if (d_ok) launch_compare(l, tab, nrows);
-                         else launch_store(l, tab, nrows);
+                         launch_ptr_rows(l, d_ok ? cec::PtrSink::compare : cec::PtrSink::store,
+                                         tab, nrows, shard_len, vec_ok, d_ok, st);
                        });
   else  // no segment has an expectation: every flag is 1
     rc = preset_ok();
@@ -1661,8 +1690,8 @@ static int partial_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_t* c
     }
     if (!wanted) continue;  // nothing wanted: no row, no work, shards not counted
     if (np < k) return set_err(CEC_ETOOFEW, "fewer than k shards present");
-    auto it = gidx.find(key);
-    if (it == gidx.end()) {
+    const size_t gi = group_of(gidx, key, groups.size());
+    if (gi == groups.size()) {
       const uint8_t* f = reinterpret_cast<const uint8_t*>(key.data());
       uint8_t rd[cec::kMaxShards];
       if (!cec::survivor_set(k, c->m, f, rd))
@@ -1670,14 +1699,11 @@ static int partial_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_t* c
       bool held = false;
       for (int i = 0; i < n; ++i) held |= rd[i] && f[n + i];
       ProgPtr p;
-      if (held) {
-        int rc = get_partial(c, f, f + n, false, &p, &up.arena, nullptr, f + 2 * n);
-        if (rc) return rc;
-      }
-      it = gidx.emplace(key, groups.size()).first;
+      if (held)
+        if (int rc = get_partial(c, f, f + n, false, &p, &up.arena, nullptr, f + 2 * n)) return rc;
       groups.push_back({p, {}});
     }
-    Group& g = groups[it->second];
+    Group& g = groups[gi];
     for (int i = 0; i < n; ++i) {
       if (!key[2 * n + i]) continue;
       if (!seen.insert((uintptr_t)dp[i]).second)
@@ -1701,24 +1727,14 @@ static int partial_ptrs_impl(cec_codec* c, const uint8_t* const* src, uint8_t* c
   std::vector<PtrLaunch> launches;
   for (const Group& g : groups)
     if (g.prog && !g.segs.empty()) add_rt_rows(c, launches, *g.prog, g.segs, src, dst, false);
+  const cec::PtrSink sink = accumulate ? cec::PtrSink::accumulate : cec::PtrSink::store;
   int rc = run_ptr_table(
       c, launches, up, st, [] { return (int)CEC_OK; },
       [&](const PtrLaunch& l, const uint64_t* tab, uint32_t nrows) {
-        if (accumulate) {
-          if (l.kind != 1 ||
-              !cec::launch_xptrs_rtb(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st))
-            cec::launch_xptrs_rt(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st);
-        } else if (l.kind != 1 ||
-                   !cec::launch_ptrs_rtb(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st)) {
-          cec::launch_ptrs_rt(tab, nrows, l.rs, l.nob, shard_len, vec_ok, st);
-        }
+        launch_ptr_rows(l, sink, tab, nrows, shard_len, vec_ok, nullptr, st);
       });
-  for (uint8_t* z : zeros) {  // zero is the neutral element of the exchange's sum
-    if (rc) break;
-    const hipError_t e = hipMemsetAsync(z, 0, shard_len, st);
-    if (e != hipSuccess)
-      rc = set_err(CEC_EHIP, std::string("partial: ") + hipGetErrorString(e));
-  }
+  // zero is the neutral element of the exchange's sum
+  rc = clear_shards(rc, zeros, shard_len, st, "partial");
   evict_decode(c);
   return rc;
 }
@@ -1793,7 +1809,8 @@ int cec_xor_ptrs(cec_codec* c, uint8_t* const* dst, const uint8_t* const* src, s
       return set_err(CEC_EINVAL, "a source is a destination of the call");
   std::vector<PtrLaunch> launches(1);
   PtrLaunch& l = launches[0];
-  l = {3, 0, (uint32_t)(nsrc + 1), {}};  // rows {dst, nsrc sources}, NULL sources kept as 0
+  // rows {dst, nsrc sources}, NULL sources kept as 0
+  l = {PtrKind::xor_rows, 0, (uint32_t)(nsrc + 1), {}};
   uintptr_t bits = 0;
   for (size_t r = 0; r < nrows; ++r) {
     if (!dst[r]) continue;
@@ -2008,17 +2025,15 @@ static int acc_ptrs_impl(cec_codec* c, const uint8_t* const* in_a, const uint8_t
       else zeros.push_back(pp[o]);  // the encode of nothing
     }
     if (!nin) continue;
-    auto it = gidx.find(key);
-    if (it == gidx.end()) {
-      it = gidx.emplace(key, groups.size()).first;
-      groups.emplace_back();
-      Group& g = groups.back();
+    const size_t gi = group_of(gidx, key, groups.size());
+    if (gi == groups.size()) {
+      Group& g = groups.emplace_back();
       for (int j = 0; j < k; ++j)
         if (key[j]) g.ins.push_back(j);
       for (int o = 0; o < m; ++o)
         if (key[k + o]) g.outs.push_back(o);
     }
-    groups[it->second].segs.push_back((uint32_t)s);
+    groups[gi].segs.push_back((uint32_t)s);
   }
   for (const Group& g : groups)  // inputs may repeat (they are only read), but none is a parity
     for (uint32_t s : g.segs)
@@ -2048,7 +2063,7 @@ static int acc_ptrs_impl(cec_codec* c, const uint8_t* const* in_a, const uint8_t
         for (int j = 0; j < ni; ++j)
           for (int o = 0; o < no; ++o)
             cf.coef[(size_t)j * no + o] = c->E->v[k + g.outs[o0 + o]][g.ins[j0 + j]];
-        PtrLaunch l{4, cec::rt_bucket(no), (uint32_t)((upd ? 2 : 1) * ni + no), {},
+        PtrLaunch l{PtrKind::acc, cec::rt_bucket(no), (uint32_t)((upd ? 2 : 1) * ni + no), {},
                     (int)coefs.size()};
         l.rows.reserve(g.segs.size() * l.rs);
         for (uint32_t s : g.segs) {
@@ -2074,13 +2089,7 @@ static int acc_ptrs_impl(cec_codec* c, const uint8_t* const* in_a, const uint8_t
                            cec::launch_acc_ptrs(tab, nrows, cf.coef.data(), cf.nin, cf.nout, upd,
                                                 cf.accumulate, shard_len, vec_ok, st);
                          });
-  for (uint8_t* z : zeros) {
-    if (rc) break;
-    const hipError_t e = hipMemsetAsync(z, 0, shard_len, st);
-    if (e != hipSuccess)
-      rc = set_err(CEC_EHIP, std::string("encode_idx: ") + hipGetErrorString(e));
-  }
-  return rc;
+  return clear_shards(rc, zeros, shard_len, st, "encode_idx");
 }
 
 int cec_encode_idx_ptrs(cec_codec* c, const uint8_t* const* data, uint8_t* const* parity,

@@ -1,5 +1,5 @@
-// Device helpers shared by the HIP translation units of libcessec (kernels.hip, sha256.hip,
-// acc.hip).
+// Device helpers, and the launchers' grid-y chunking, shared by the HIP translation units of
+// libcessec.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,6 +28,15 @@ __device__ __forceinline__ const cu64* tab_row(const uint64_t* tab, uint64_t row
   return (const cu64*)(uintptr_t)tab + row * rs;
 }
 __device__ __forceinline__ gu8* gptr(uint64_t a) { return (gu8*)a; }
+
+// Host: a grid is at most kMaxGridY workgroup rows high, so `n` rows (segments, table rows,
+// fragments) take f(first row, row count) once per launch of at most that many.
+constexpr uint32_t kMaxGridY = 65535;
+template <class F>
+void for_y_chunks(uint64_t n, F f) {
+  for (uint64_t r0 = 0; r0 < n; r0 += kMaxGridY)
+    f((uint32_t)r0, (uint32_t)(n - r0 < kMaxGridY ? n - r0 : kMaxGridY));
+}
 
 // v_bitop3 with truth table 0x96: a ^ b ^ c in one VALU op.
 __device__ __forceinline__ uint32_t xor3_u32(uint32_t a, uint32_t b, uint32_t c) {

@@ -110,10 +110,9 @@ bool launch_fft_rs3232_verify(const Layout& L, uint8_t* ok, uint32_t nseg, hipSt
                          L.data_seg_stride | L.par_seg_stride;
   if ((bits & 15) || (L.len & 1023) || L.len == 0 || L.k != 32) return false;
   const uint64_t gx = (L.len / 32 * 2 + 255) / 256;
-  for (uint32_t s0 = 0; s0 < nseg; s0 += 65535) {
-    const uint32_t ny = nseg - s0 < 65535 ? nseg - s0 : 65535;
+  for_y_chunks(nseg, [&](uint32_t s0, uint32_t ny) {
     hipLaunchKernelGGL(k_fft3232_verify, dim3((unsigned)gx, ny), dim3(256), 0, st, L, ok, s0);
-  }
+  });
   return true;
 }
 
@@ -147,8 +146,7 @@ bool launch_fft_rs3232(const Layout& L, const uint32_t* seg_list, uint32_t nseg,
   const uint64_t lanes = L.len / 32 * 2;
   const uint64_t gx = (lanes + 255) / 256;
   [[maybe_unused]] const int cpw = (nt >> 5) & 15;  // tuning build: column blocks per workgroup (0: 1)
-  for (uint32_t s0 = 0; s0 < nseg; s0 += 65535) {
-    const uint32_t ny = nseg - s0 < 65535 ? nseg - s0 : 65535;
+  for_y_chunks(nseg, [&](uint32_t s0, uint32_t ny) {
     // nt: bit 0 = nontemporal loads, bit 1 = nontemporal stores; tuning build only: bits 2-3 =
     // DIAG, bit 4 = 48 KiB of LDS per workgroup (caps a CU at 3 workgroups = 3 waves per SIMD)
     switch (nt & 3) {
@@ -198,7 +196,7 @@ bool launch_fft_rs3232(const Layout& L, const uint32_t* seg_list, uint32_t nseg,
         hipLaunchKernelGGL((k_fft3232<false, false>), dim3((unsigned)gx, ny), dim3(256), 0, st, L,
                            seg_list, s0);
     }
-  }
+  });
   return true;
 }
 

@@ -344,11 +344,10 @@ bool launch_fftdec(const Layout& L, int side, bool big, const uint32_t* plan1,
 #else
   (void)form;
 #endif
-  for (uint32_t s0 = 0; s0 < nseg; s0 += 65535) {
-    const uint32_t ny = nseg - s0 < 65535 ? nseg - s0 : 65535;
+  for_y_chunks(nseg, [&](uint32_t s0, uint32_t ny) {
     hipLaunchKernelGGL(kern, dim3((unsigned)gx, ny), dim3(256), 0, st, L, plan1, plans, seg_list,
                        s0);
-  }
+  });
   return true;
 }
 

@@ -131,41 +131,31 @@ bool launch_matvec_rth(const KernelOpts& o, const Layout& L, const uint32_t* chu
                        const uint32_t* const* per_seg, int nin_max, const uint32_t* seg_list,
                        uint32_t nseg, hipStream_t st);
 
-// Pointer-table addressing (scattered shards, cec_reconstruct_ptrs): `tab` holds `nrows` rows of
+// Pointer-table addressing (scattered shards, the cec_*_ptrs calls): `tab` holds `nrows` rows of
 // 64-bit words in HBM, one per workgroup row, the device addresses of a segment's inputs in
 // program order, then of its outputs, each `len` bytes. vec_ok: every address in the rows is
 // 16-byte aligned (else the byte path runs for the whole launch).
-// RS(2,1), compile-time coefficients: row = {input 0, input 1, output, case}, case 0 / 1 = rebuild
-// data fragment 0 / 1 from (the other data fragment, the parity), 2 = encode from (d0, d1).
-void launch_ptrs_rs21(const uint64_t* tab, uint32_t nrows, uint64_t len, bool vec_ok,
-                      hipStream_t st);
+// What a launch does with the `len` bytes at every output position of its rows:
+enum class PtrSink {
+  store,      // writes the product there (rebuild, encode)
+  compare,    // reads them as the expected bytes and compares: ok[segment] (device, preset to 1 by
+              // the caller) = 0 for a row that differs, and nothing else is written. The rows
+              // carry their segment (below). `ok` is read by this sink only.
+  accumulate  // reads them, XORs the product in and writes them back
+};
+// RS(2,1), compile-time coefficients: row = {input 0, input 1, output, case} (compare: case |
+// segment << 32), case 0 / 1 = rebuild data fragment 0 / 1 from (the other data fragment, the
+// parity), 2 = encode from (d0, d1). Store and compare only (partials take the run-time rows):
+// nothing is launched for accumulate.
+void launch_ptrs_rs21(PtrSink sink, const uint64_t* tab, uint32_t nrows, uint64_t len, bool vec_ok,
+                      uint8_t* ok, hipStream_t st);
 // Run-time programs: row = {address of the segment's program chunk, its nin inputs, its nout
-// outputs}, rows `rs` words apart (rs >= 1 + nin + nout), every chunk of the launch of bucket
-// `nob`. _rtb: the bit-plane product for nob <= 4 (false, nothing launched, for a wider bucket);
-// _rt: the per-bit mask product for any bucket.
-bool launch_ptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
-                     bool vec_ok, hipStream_t st);
-void launch_ptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
-                    bool vec_ok, hipStream_t st);
-// The compare forms of the three (cec_verify_ptrs): the addresses in the output positions name
-// the expected bytes, which are read and compared with the product instead of written; ok[segment]
-// (device, preset to 1 by the caller) = 0 for a row that differs, and nothing else is written.
-// Rows carry their segment: RS(2,1) row = {input 0, input 1, expected, case | segment << 32};
-// run-time row = {program chunk, nin inputs, nout expected, ..., segment}, the segment in word
-// rs - 1 (rs >= 2 + nin + nout).
-void launch_vptrs_rs21(const uint64_t* tab, uint32_t nrows, uint64_t len, bool vec_ok, uint8_t* ok,
-                       hipStream_t st);
-bool launch_vptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
-                      bool vec_ok, uint8_t* ok, hipStream_t st);
-void launch_vptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
-                     bool vec_ok, uint8_t* ok, hipStream_t st);
-// The accumulate forms of the two run-time ones (cec_reconstruct_partial_ptrs with accumulate):
-// rows as in the store forms; the len bytes at every output address are read, XORed with the
-// product and written back.
-bool launch_xptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
-                      bool vec_ok, hipStream_t st);
-void launch_xptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
-                     bool vec_ok, hipStream_t st);
+// outputs, ..., segment}, rows `rs` words apart (rs >= 1 + nin + nout; compare: the segment in
+// word rs - 1, rs >= 2 + nin + nout), every chunk of the launch of bucket `nob`. The per-bit mask
+// product (k_rt's) for any bucket, or with `bitplane` the bit-plane product (k_rtb's) where the
+// bucket has one (nob <= 4).
+void launch_ptrs_rt(PtrSink sink, bool bitplane, const uint64_t* tab, uint32_t nrows, uint32_t rs,
+                    int nob, uint64_t len, bool vec_ok, uint8_t* ok, hipStream_t st);
 
 // SHA-256 of `n` equal-length buffers, written as 64 lowercase hex characters each into
 // `hex_out` (device, n * 64 bytes). If `ptrs` is null, buffer i is shard (i % nshards) of

@@ -18,6 +18,7 @@
 //    (acc ^= pow_b & mask_b).
 // Each lane owns 16-byte columns (global_load_dwordx4) of every shard; blockIdx.y is the
 // segment. A shard length that is not a multiple of 16 is finished byte-wise by the last block.
+#include <type_traits>
 #include <utility>
 
 #include "dev_util.h"
@@ -1388,13 +1389,6 @@ bool layout_vec16_ok(const Layout& L) {
 
 namespace {
 
-constexpr uint32_t kMaxGridY = 65535;
-
-template <class F>
-void for_seg_chunks(uint32_t nseg, F f) {
-  for (uint32_t s0 = 0; s0 < nseg; s0 += kMaxGridY) f(s0, nseg - s0 < kMaxGridY ? nseg - s0 : kMaxGridY);
-}
-
 // Grid width of the run-time and pointer-table kernels: blocks of 256 lanes with `u` columns of
 // `vb` bytes each (the last block also takes the tail), or of 256 bytes on the all-byte path.
 unsigned rt_grid_x(uint64_t len, size_t vb, int u, bool vec_ok) {
@@ -1444,13 +1438,13 @@ void run_ct(const Layout& L, const uint32_t* seg_list, uint32_t nseg, hipStream_
     const uint64_t nvec = L.len / sizeof(TV);
     uint64_t gx = (nvec + BS * U - 1) / (BS * U);
     if (gx == 0) gx = 1;  // tail-only shard
-    for_seg_chunks(nseg, [&](uint32_t s0, uint32_t ny) CEC_AI {
+    for_y_chunks(nseg, [&](uint32_t s0, uint32_t ny) CEC_AI {
       hipLaunchKernelGGL((k_ct<P, U, NT, TV, PF, WIN, BS>), dim3((unsigned)gx, ny), dim3(BS), 0,
                          st, L, seg_list, s0);
     });
   } else {
     const uint64_t gx = (L.len + 255) / 256;
-    for_seg_chunks(nseg, [&](uint32_t s0, uint32_t ny) CEC_AI {
+    for_y_chunks(nseg, [&](uint32_t s0, uint32_t ny) CEC_AI {
       hipLaunchKernelGGL((k_ct_bytes<P>), dim3((unsigned)gx, ny), dim3(256), 0, st, L, seg_list,
                          s0);
     });
@@ -1510,7 +1504,7 @@ void run_hg(const Layout& L, const uint32_t* seg_list, uint32_t nseg, hipStream_
   }
   uint64_t gx = (L.len / 4 + BS - 1) / BS;
   if (gx == 0) gx = 1;
-  for_seg_chunks(nseg, [&](uint32_t s0, uint32_t ny) CEC_AI {
+  for_y_chunks(nseg, [&](uint32_t s0, uint32_t ny) CEC_AI {
     hipLaunchKernelGGL((k_hg<P, G, FL, BS>), dim3((unsigned)gx, ny), dim3(BS), 0, st, L,
                        seg_list, s0);
   });
@@ -1613,7 +1607,7 @@ bool launch_verify_ct(int k, int m, const Layout& L, uint8_t* ok, uint32_t nseg,
   if (k == 32 && m == 32) return launch_fft_rs3232_verify(L, ok, nseg, st);
   if (k != 2 || m != 1 || !layout_vec16_ok(L) || (L.len & 15)) return false;
   const uint64_t gx = (L.len / 16 + 255) / 256;
-  for_seg_chunks(nseg, [&](uint32_t s0, uint32_t ny) CEC_AI {
+  for_y_chunks(nseg, [&](uint32_t s0, uint32_t ny) CEC_AI {
     hipLaunchKernelGGL(k_verify21, dim3((unsigned)gx, ny), dim3(256), 0, st, L, ok, s0);
   });
   return true;
@@ -1625,7 +1619,7 @@ bool launch_decode1_mixed(const KernelOpts& o, int k, int m, const Layout& L,
   if (k != 2 || m != 1 || o.ct_variant != -1 || !layout_vec16_ok(L)) return false;
   uint64_t gx = (L.len / 16 + 255) / 256;
   if (gx == 0) gx = 1;
-  for_seg_chunks(nseg, [&](uint32_t s0, uint32_t ny) CEC_AI {
+  for_y_chunks(nseg, [&](uint32_t s0, uint32_t ny) CEC_AI {
     hipLaunchKernelGGL((k_ct_dec1_mixed21<true, 256>), dim3((unsigned)gx, ny), dim3(256), 0, st,
                        L, tagged, s0);
   });
@@ -1699,7 +1693,7 @@ void run_rt(const Layout& L, const uint32_t* chunk, const uint32_t* const* per_s
             const uint32_t* seg_list, uint32_t nseg, hipStream_t st) {
   const int vec_ok = layout_vec16_ok(L) ? 1 : 0;
   const unsigned gx = rt_grid_x(L.len, sizeof(TV), U, vec_ok);
-  for_seg_chunks(nseg, [&](uint32_t s0, uint32_t ny) {
+  for_y_chunks(nseg, [&](uint32_t s0, uint32_t ny) {
     hipLaunchKernelGGL((k_rt<NOB, U, TV>), dim3(gx, ny), dim3(256), 0, st, L, chunk, per_seg,
                        seg_list, s0, vec_ok);
   });
@@ -1719,7 +1713,7 @@ void run_rtb(const Layout& L, const uint32_t* chunk, const uint32_t* const* per_
              const uint32_t* seg_list, uint32_t nseg, hipStream_t st) {
   const int vec_ok = layout_vec16_ok(L) ? 1 : 0;
   const unsigned gx = rt_grid_x(L.len, sizeof(TV), 1, vec_ok);
-  for_seg_chunks(nseg, [&](uint32_t s0, uint32_t ny) {
+  for_y_chunks(nseg, [&](uint32_t s0, uint32_t ny) {
     hipLaunchKernelGGL((k_rtb<NOB, TV, PF>), dim3(gx, ny), dim3(256), 0, st, L, chunk, per_seg,
                        seg_list, s0, vec_ok);
   });
@@ -1777,7 +1771,7 @@ void run_rth(int rt_mode, const Layout& L, const uint32_t* chunk, const uint32_t
   const int vec_ok = (bits & 3) == 0;
   uint64_t gx = vec_ok ? (L.len / 4 + 255) / 256 : (L.len + 255) / 256;
   if (gx == 0) gx = 1;
-  for_seg_chunks(nseg, [&](uint32_t s0, uint32_t ny) {
+  for_y_chunks(nseg, [&](uint32_t s0, uint32_t ny) {
     if (rt_mode == 0)
       hipLaunchKernelGGL((k_rthx<NG>), dim3((unsigned)gx, ny), dim3(256), 0, st, L, chunk,
                          per_seg, seg_list, s0, vec_ok);
@@ -1865,9 +1859,26 @@ __device__ __forceinline__ void ptr_tile21(gu8* i0, gu8* i1, gu8* o0, uint64_t l
   sink.flush();
 }
 
-template <bool NT>
+// What a kernel of the family does with the output positions of its row is its Sink (kernels.h
+// PtrSink), made from the launch's sink arguments SA: none for StoreSink and XorSink, the flags
+// `ok` for CmpSink, whose rows say which segment they belong to (several rows of one segment, one
+// per program chunk, share a flag). seg() reads that word and only CmpSink calls it: RS(2,1) keeps
+// it in the high half of the case word, {input 0, input 1, expected, case | segment << 32}; the
+// run-time rows in one more word at their end, {program chunk, nin inputs, nout expected,
+// (padding up to rs - 1,) segment}, which leaves TableAddr's view of the row as it is. A compare
+// launch's only store is the 0 into ok[segment] of a row that differs.
+__device__ __forceinline__ CmpSink cmp_sink(uint8_t* ok, uint64_t seg) {
+  return CmpSink{gptr((uint64_t)(uintptr_t)ok) + seg};
+}
+template <class Sink, class Seg, class... SA>
+__device__ __forceinline__ Sink row_sink(Seg seg, SA... sa) {
+  if constexpr (std::is_same_v<Sink, CmpSink>) return cmp_sink(sa..., seg());
+  else return Sink{};
+}
+
+template <bool NT, class Sink, class... SA>
 __global__ __launch_bounds__(256) void k_ptr21(const uint64_t* __restrict__ tab, uint32_t row0,
-                                               uint64_t len, int vec_ok) {
+                                               uint64_t len, int vec_ok, SA... sa) {
   const cu64* __restrict__ row = tab_row(tab, row0 + blockIdx.y, 4);
   // the whole row in one scalar load ahead of the case branch: the addresses are then one
   // scalar-cache round trip from the first global load, not two
@@ -1875,164 +1886,76 @@ __global__ __launch_bounds__(256) void k_ptr21(const uint64_t* __restrict__ tab,
   gu8* const i1 = gptr(row[1]);
   gu8* const o0 = gptr(row[2]);
   const uint32_t e = (uint32_t)row[3];
-  if (e == 0) ptr_tile21<Dec1CT<2, 1, 0>, NT>(i0, i1, o0, len, vec_ok);
-  else if (e == 1) ptr_tile21<Dec1CT<2, 1, 1>, NT>(i0, i1, o0, len, vec_ok);
-  else if (e == 2) ptr_tile21<EncCT<2, 1>, NT>(i0, i1, o0, len, vec_ok);
+  const Sink sink = row_sink<Sink>([&]() CEC_AI { return row[3] >> 32; }, sa...);
+  if (e == 0) ptr_tile21<Dec1CT<2, 1, 0>, NT>(i0, i1, o0, len, vec_ok, sink);
+  else if (e == 1) ptr_tile21<Dec1CT<2, 1, 1>, NT>(i0, i1, o0, len, vec_ok, sink);
+  else if (e == 2) ptr_tile21<EncCT<2, 1>, NT>(i0, i1, o0, len, vec_ok, sink);
 }
 
 // Run-time coefficients: row = {program chunk, nin inputs, nout outputs} (TableAddr), rows of a
 // launch `rs` words apart. k_ptrt is k_rt's product, k_ptrb k_rtb's.
-template <int NOB, int U, class TV>
+template <int NOB, int U, class TV, class Sink, class... SA>
 __global__ __launch_bounds__(256) void k_ptrt(const uint64_t* __restrict__ tab, uint32_t row0,
-                                              uint32_t rs, uint64_t len, int vec_ok) {
-  rt_body<NOB, U, TV, TableAddr>(TableAddr(tab, row0 + blockIdx.y, rs, len), vec_ok);
+                                              uint32_t rs, uint64_t len, int vec_ok, SA... sa) {
+  const uint64_t r = row0 + blockIdx.y;
+  rt_body<NOB, U, TV, TableAddr>(
+      TableAddr(tab, r, rs, len), vec_ok,
+      row_sink<Sink>([&]() CEC_AI { return tab_row(tab, r, rs)[rs - 1]; }, sa...));
 }
 
-template <int NOB, class TV, int PF>
+template <int NOB, class TV, int PF, class Sink, class... SA>
 __global__ __launch_bounds__(256) void k_ptrb(const uint64_t* __restrict__ tab, uint32_t row0,
-                                              uint32_t rs, uint64_t len, int vec_ok) {
-  rtb_body<NOB, TV, PF, TableAddr>(TableAddr(tab, row0 + blockIdx.y, rs, len), vec_ok);
-}
-
-void launch_ptrs_rs21(const uint64_t* tab, uint32_t nrows, uint64_t len, bool vec_ok,
-                      hipStream_t st) {
-  const unsigned gx = rt_grid_x(len, 16, 1, vec_ok);
-  for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
-    hipLaunchKernelGGL((k_ptr21<true>), dim3(gx, ny), dim3(256), 0, st, tab, r0, len,
-                       vec_ok ? 1 : 0);
-  });
-}
-
-bool launch_ptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
-                     bool vec_ok, hipStream_t st) {
-  return rtb_dispatch(nob, [&]<int NOB, class TV, int PF>(RtbShape<NOB, TV, PF>) {
-    const unsigned gx = rt_grid_x(len, sizeof(TV), 1, vec_ok);
-    for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
-      hipLaunchKernelGGL((k_ptrb<NOB, TV, PF>), dim3(gx, ny), dim3(256), 0, st, tab, r0, rs, len,
-                         vec_ok ? 1 : 0);
-    });
-  });
-}
-
-void launch_ptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
-                    bool vec_ok, hipStream_t st) {
-  rt_dispatch(nob, [&]<int NOB, int U, class TV>(RtShape<NOB, U, TV>) {
-    const unsigned gx = rt_grid_x(len, sizeof(TV), U, vec_ok);
-    for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
-      hipLaunchKernelGGL((k_ptrt<NOB, U, TV>), dim3(gx, ny), dim3(256), 0, st, tab, r0, rs, len,
-                         vec_ok ? 1 : 0);
-    });
-  });
-}
-
-// The compare forms (cec_verify_ptrs): the same tile and products with CmpSink, so the addresses
-// in the output positions of a row are read, not written, and the only store of a launch is the
-// 0 into ok[segment] of a row that differs (ok preset to 1 by the caller). The rows say which
-// segment they belong to (several rows of one segment, one per program chunk, share a flag):
-// RS(2,1) in the high half of the case word, {input 0, input 1, expected, case | segment << 32};
-// the run-time rows in one more word at their end, {program chunk, nin inputs, nout expected,
-// (padding up to rs - 1,) segment}, which leaves TableAddr's view of the row as it is.
-__device__ __forceinline__ CmpSink cmp_sink(uint8_t* ok, uint64_t seg) {
-  return CmpSink{gptr((uint64_t)(uintptr_t)ok) + seg};
-}
-
-template <bool NT>
-__global__ __launch_bounds__(256) void k_ptr21v(const uint64_t* __restrict__ tab, uint32_t row0,
-                                                uint64_t len, int vec_ok, uint8_t* ok) {
-  const cu64* __restrict__ row = tab_row(tab, row0 + blockIdx.y, 4);
-  gu8* const i0 = gptr(row[0]);
-  gu8* const i1 = gptr(row[1]);
-  gu8* const x0 = gptr(row[2]);
-  const uint32_t e = (uint32_t)row[3];
-  const CmpSink sink = cmp_sink(ok, row[3] >> 32);
-  if (e == 0) ptr_tile21<Dec1CT<2, 1, 0>, NT>(i0, i1, x0, len, vec_ok, sink);
-  else if (e == 1) ptr_tile21<Dec1CT<2, 1, 1>, NT>(i0, i1, x0, len, vec_ok, sink);
-  else if (e == 2) ptr_tile21<EncCT<2, 1>, NT>(i0, i1, x0, len, vec_ok, sink);
-}
-
-template <int NOB, int U, class TV>
-__global__ __launch_bounds__(256) void k_ptrtv(const uint64_t* __restrict__ tab, uint32_t row0,
-                                               uint32_t rs, uint64_t len, int vec_ok,
-                                               uint8_t* ok) {
+                                              uint32_t rs, uint64_t len, int vec_ok, SA... sa) {
   const uint64_t r = row0 + blockIdx.y;
-  rt_body<NOB, U, TV, TableAddr>(TableAddr(tab, r, rs, len), vec_ok,
-                                 cmp_sink(ok, tab_row(tab, r, rs)[rs - 1]));
+  rtb_body<NOB, TV, PF, TableAddr>(
+      TableAddr(tab, r, rs, len), vec_ok,
+      row_sink<Sink>([&]() CEC_AI { return tab_row(tab, r, rs)[rs - 1]; }, sa...));
 }
 
-template <int NOB, class TV, int PF>
-__global__ __launch_bounds__(256) void k_ptrbv(const uint64_t* __restrict__ tab, uint32_t row0,
-                                               uint32_t rs, uint64_t len, int vec_ok,
-                                               uint8_t* ok) {
-  const uint64_t r = row0 + blockIdx.y;
-  rtb_body<NOB, TV, PF, TableAddr>(TableAddr(tab, r, rs, len), vec_ok,
-                                   cmp_sink(ok, tab_row(tab, r, rs)[rs - 1]));
+namespace {
+// A launch's sink as a type: f(SinkTag<Sink>, the sink's kernel arguments...).
+template <class Sink>
+struct SinkTag {};
+template <class F>
+void sink_dispatch(PtrSink sink, uint8_t* ok, F f) {
+  switch (sink) {
+    case PtrSink::store: f(SinkTag<StoreSink>{}); break;
+    case PtrSink::compare: f(SinkTag<CmpSink>{}, ok); break;
+    case PtrSink::accumulate: f(SinkTag<XorSink>{}); break;
+  }
 }
 
-void launch_vptrs_rs21(const uint64_t* tab, uint32_t nrows, uint64_t len, bool vec_ok, uint8_t* ok,
-                       hipStream_t st) {
+// Table kernel k over `nrows` rows, `gx` blocks wide: k(tab, first row, a...) per grid-y chunk.
+template <class K, class... A>
+void launch_rows(K k, unsigned gx, const uint64_t* tab, uint32_t nrows, hipStream_t st, A... a) {
+  for_y_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
+    hipLaunchKernelGGL(k, dim3(gx, ny), dim3(256), 0, st, tab, r0, a...);
+  });
+}
+}  // namespace
+
+void launch_ptrs_rs21(PtrSink sink, const uint64_t* tab, uint32_t nrows, uint64_t len, bool vec_ok,
+                      uint8_t* ok, hipStream_t st) {
   const unsigned gx = rt_grid_x(len, 16, 1, vec_ok);
-  for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
-    hipLaunchKernelGGL((k_ptr21v<true>), dim3(gx, ny), dim3(256), 0, st, tab, r0, len,
-                       vec_ok ? 1 : 0, ok);
-  });
+  const int v = vec_ok ? 1 : 0;
+  if (sink == PtrSink::store)
+    launch_rows(k_ptr21<true, StoreSink>, gx, tab, nrows, st, len, v);
+  else if (sink == PtrSink::compare)
+    launch_rows(k_ptr21<true, CmpSink, uint8_t*>, gx, tab, nrows, st, len, v, ok);
 }
 
-bool launch_vptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
-                      bool vec_ok, uint8_t* ok, hipStream_t st) {
-  return rtb_dispatch(nob, [&]<int NOB, class TV, int PF>(RtbShape<NOB, TV, PF>) {
-    const unsigned gx = rt_grid_x(len, sizeof(TV), 1, vec_ok);
-    for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
-      hipLaunchKernelGGL((k_ptrbv<NOB, TV, PF>), dim3(gx, ny), dim3(256), 0, st, tab, r0, rs, len,
-                         vec_ok ? 1 : 0, ok);
-    });
-  });
-}
-
-void launch_vptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
-                     bool vec_ok, uint8_t* ok, hipStream_t st) {
-  rt_dispatch(nob, [&]<int NOB, int U, class TV>(RtShape<NOB, U, TV>) {
-    const unsigned gx = rt_grid_x(len, sizeof(TV), U, vec_ok);
-    for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
-      hipLaunchKernelGGL((k_ptrtv<NOB, U, TV>), dim3(gx, ny), dim3(256), 0, st, tab, r0, rs, len,
-                         vec_ok ? 1 : 0, ok);
-    });
-  });
-}
-
-// The accumulate forms (cec_reconstruct_partial_ptrs with accumulate): the same products with
-// XorSink, so every output address of a row is read, XORed with the product and written back.
-// Rows are those of the store forms, {program chunk, nin inputs, nout outputs}. Partials always
-// take the run-time kernels, so RS(2,1) has no compile-time form here.
-template <int NOB, int U, class TV>
-__global__ __launch_bounds__(256) void k_ptrtx(const uint64_t* __restrict__ tab, uint32_t row0,
-                                               uint32_t rs, uint64_t len, int vec_ok) {
-  rt_body<NOB, U, TV, TableAddr>(TableAddr(tab, row0 + blockIdx.y, rs, len), vec_ok, XorSink{});
-}
-
-template <int NOB, class TV, int PF>
-__global__ __launch_bounds__(256) void k_ptrbx(const uint64_t* __restrict__ tab, uint32_t row0,
-                                               uint32_t rs, uint64_t len, int vec_ok) {
-  rtb_body<NOB, TV, PF, TableAddr>(TableAddr(tab, row0 + blockIdx.y, rs, len), vec_ok, XorSink{});
-}
-
-bool launch_xptrs_rtb(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
-                      bool vec_ok, hipStream_t st) {
-  return rtb_dispatch(nob, [&]<int NOB, class TV, int PF>(RtbShape<NOB, TV, PF>) {
-    const unsigned gx = rt_grid_x(len, sizeof(TV), 1, vec_ok);
-    for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
-      hipLaunchKernelGGL((k_ptrbx<NOB, TV, PF>), dim3(gx, ny), dim3(256), 0, st, tab, r0, rs, len,
-                         vec_ok ? 1 : 0);
-    });
-  });
-}
-
-void launch_xptrs_rt(const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob, uint64_t len,
-                     bool vec_ok, hipStream_t st) {
-  rt_dispatch(nob, [&]<int NOB, int U, class TV>(RtShape<NOB, U, TV>) {
-    const unsigned gx = rt_grid_x(len, sizeof(TV), U, vec_ok);
-    for_seg_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
-      hipLaunchKernelGGL((k_ptrtx<NOB, U, TV>), dim3(gx, ny), dim3(256), 0, st, tab, r0, rs, len,
-                         vec_ok ? 1 : 0);
+void launch_ptrs_rt(PtrSink sink, bool bitplane, const uint64_t* tab, uint32_t nrows, uint32_t rs,
+                    int nob, uint64_t len, bool vec_ok, uint8_t* ok, hipStream_t st) {
+  const int v = vec_ok ? 1 : 0;
+  sink_dispatch(sink, ok, [&]<class Sink, class... SA>(SinkTag<Sink>, SA... sa) {
+    if (bitplane && rtb_dispatch(nob, [&]<int NOB, class TV, int PF>(RtbShape<NOB, TV, PF>) {
+          launch_rows(k_ptrb<NOB, TV, PF, Sink, SA...>, rt_grid_x(len, sizeof(TV), 1, vec_ok), tab,
+                      nrows, st, rs, len, v, sa...);
+        }))
+      return;
+    rt_dispatch(nob, [&]<int NOB, int U, class TV>(RtShape<NOB, U, TV>) {
+      launch_rows(k_ptrt<NOB, U, TV, Sink, SA...>, rt_grid_x(len, sizeof(TV), U, vec_ok), tab,
+                  nrows, st, rs, len, v, sa...);
     });
   });
 }

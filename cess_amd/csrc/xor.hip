@@ -92,11 +92,10 @@ void launch_xor_rows(const uint64_t* tab, uint32_t nrows, uint32_t nsrc, uint64_
   if (len == 0 || nsrc == 0 || nrows == 0) return;
   uint64_t gx = vec_ok ? (len / 16 + 255) / 256 : (len + 255) / 256;
   if (gx == 0) gx = 1;  // shorter than one column: the tail's block
-  for (uint32_t r0 = 0; r0 < nrows; r0 += 65535) {
-    const uint32_t ny = nrows - r0 < 65535 ? nrows - r0 : 65535;
+  for_y_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
     hipLaunchKernelGGL(k_xor_rows, dim3((uint32_t)gx, ny), dim3(256), 0, st, tab, r0, nsrc, len,
                        vec_ok ? 1 : 0);
-  }
+  });
 }
 
 // Per-segment equality of two [nseg][seg_bytes] device arrays (cec_verify_batch: recomputed
@@ -131,15 +130,14 @@ void launch_cmp_segments(const uint8_t* a, const uint8_t* b, uint64_t seg_bytes,
   const bool v16 = (((uintptr_t)a | (uintptr_t)b | seg_bytes) & 15) == 0;
   const uint64_t per_block = v16 ? 256 * 16 : 256;
   const uint64_t gx = (seg_bytes + per_block - 1) / per_block;
-  for (uint64_t s0 = 0; s0 < nseg; s0 += 65535) {
-    const uint32_t ny = (uint32_t)(nseg - s0 < 65535 ? nseg - s0 : 65535);
+  for_y_chunks(nseg, [&](uint32_t s0, uint32_t ny) {
     if (v16)
       hipLaunchKernelGGL(k_cmp_segments<true>, dim3((uint32_t)gx, ny), dim3(256), 0, st, a, b,
-                         seg_bytes, ok, (uint32_t)s0);
+                         seg_bytes, ok, s0);
     else
       hipLaunchKernelGGL(k_cmp_segments<false>, dim3((uint32_t)gx, ny), dim3(256), 0, st, a, b,
-                         seg_bytes, ok, (uint32_t)s0);
-  }
+                         seg_bytes, ok, s0);
+  });
 }
 
 }  // namespace cec

@@ -127,6 +127,14 @@ def _dev_ptr(t) -> int:
     return t.data_ptr()
 
 
+def _on_gpu(t, dev):
+    """Tensor t, refused unless it lives on the codec's GPU `dev` (_dev_ptr refuses host and
+    strided tensors)."""
+    if t.device != dev:
+        raise TypeError("device shards must live on the codec's GPU")
+    return t
+
+
 def _stream_handle(stream) -> Optional[int]:
     if stream is None:
         return None
@@ -457,9 +465,7 @@ class Encoder:
             for i, t in enumerate(shards):
                 if t is None:
                     continue
-                if t.device != dev:  # (_dev_ptr below refuses host and strided tensors)
-                    raise TypeError("device shards must live on the codec's GPU")
-                held.append(t)
+                held.append(_on_gpu(t, dev))
                 (exp if flags[i] else src)[s * n + i] = _dev_ptr(t)
         size = self._check_device_shards(held)
         _check_rc(self._lib.cec_verify_ptrs(self._h, src, exp, nseg, size, _dev_ptr(d_ok),
@@ -515,9 +521,7 @@ class Encoder:
         used = []
 
         def addr(t):
-            if t.device != dev:  # (_dev_ptr refuses host and strided tensors)
-                raise TypeError("device shards must live on the codec's GPU")
-            used.append(t)
+            used.append(_on_gpu(t, dev))
             return _dev_ptr(t)
 
         for s, shards in enumerate(segments):
@@ -561,9 +565,7 @@ class Encoder:
             for j, t in enumerate(row):
                 if t is None:
                     continue
-                if t.device != dev:
-                    raise TypeError("device shards must live on the codec's GPU")
-                used.append(t)
+                used.append(_on_gpu(t, dev))
                 if j == 0:
                     d[r] = _dev_ptr(t)
                 else:
@@ -661,8 +663,8 @@ class Encoder:
             return
         import torch
         dev = torch.device("cuda", self.device)
-        if any(t.device != dev for t in used):  # (_dev_ptr refuses host and strided tensors)
-            raise TypeError("device shards must live on the codec's GPU")
+        for t in used:
+            _on_gpu(t, dev)
         a = (c_void_p * (nseg * k))()
         b = (c_void_p * (nseg * k))()
         p = (c_void_p * (nseg * m))()

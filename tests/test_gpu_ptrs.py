@@ -428,6 +428,44 @@ def test_table_and_layout_kernels_agree(torch, cess, corc, mode, nlost, ln, off)
                 assert np.array_equal(table, uniform[0, i]), (i, "table != uniform")
 
 
+# ---- rows past the grid-y limit -------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("k,m,rt_mode", [(2, 1, None), (4, 2, None), (4, 2, 1)])
+def test_rows_past_the_grid_limit(torch, cess, corc, k, m, rt_mode):
+    """65,537 segments of 16 bytes, past the 65,535-row split of a launch, that share one
+    codeword's tensors as sources; data shard 0 is lost and only it is wanted, into distinct slices
+    of one tensor with a guard slice at either end. RS(2,1): k_ptr21; RS(4,2): k_ptrb<1> (four
+    inputs, one output), and with CEC_OPT_RT_MODE 1 k_ptrt<1>."""
+    from cess_amd import _lib
+    n, ln, nseg = k + m, 16, 65537
+    full = codewords(corc, k, m, ln, 1)[0]
+    present = np.ones(n, dtype=np.uint8)
+    present[0] = 0
+    surv = survivors(cess, k, m, present)
+    rng = np.random.default_rng(4100 + 10 * k + (rt_mode or 0))
+    held = {i: (full[i].copy() if i in surv else rng.integers(0, 256, ln, dtype=np.uint8))
+            for i in range(1, n)}
+    dev = {i: torch.from_numpy(h).cuda() for i, h in held.items()}
+    fill = rng.integers(0, 256, (nseg + 2, ln), dtype=np.uint8)
+    out = torch.from_numpy(fill).cuda()
+    base = out.data_ptr() + ln
+    src = ([None] + [dev[i].data_ptr() for i in range(1, n)]) * nseg
+    dst = [x for s in range(nseg) for x in [base + s * ln] + [None] * (n - 1)]
+    a, b = (c_void_p * len(src))(*src), (c_void_p * len(dst))(*dst)
+    enc = cess.New(k, m)
+    if rt_mode is not None:
+        enc.set_option(_lib.CEC_OPT_RT_MODE, rt_mode)
+    assert _lib.load().cec_reconstruct_ptrs(enc._h, a, b, nseg, ln, None) == 0
+    torch.cuda.synchronize()
+    want = fill.copy()
+    want[1:-1] = full[0]
+    got = out.cpu().numpy()
+    assert np.array_equal(got, want), np.flatnonzero((got != want).any(axis=1))[:8]
+    for i, h in held.items():
+        assert np.array_equal(dev[i].cpu().numpy(), h), (i, "a source was written")
+
+
 # ---- past kRtMaxOut outputs, and the widest geometry ---------------------------------------------
 
 

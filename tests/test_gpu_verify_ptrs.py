@@ -232,6 +232,37 @@ def test_grid_chunking(torch, cess, corc):
     assert torch.equal(before, torch.cat(bufs))
 
 
+@pytest.mark.parametrize("rt_mode", [None, 1])
+def test_grid_chunking_run_time_rows(torch, cess, corc, rt_mode):
+    """65,537 RS(4,2) segments of 16 bytes, all aliasing the same buffers, past the 65,535-row
+    split of a launch: data shard 0 expected from the four survivors, by k_ptrb<1> and, with
+    CEC_OPT_RT_MODE 1, by k_ptrt<1>; only the last segment expects a copy with one flipped bit."""
+    from cess_amd import _lib
+    k, m, ln, nseg = 4, 2, 16, 65537
+    n = k + m
+    full = codewords(corc, k, m, ln, 1)[0]
+    surv = [torch.from_numpy(full[i].copy()).cuda() for i in range(1, k + 1)]
+    good = torch.from_numpy(full[0].copy()).cuda()
+    bad = good.clone()
+    bad[5] ^= 0x10
+    bufs = surv + [good, bad]
+    src = ([None] + [t.data_ptr() for t in surv] + [None] * (m - 1)) * nseg
+    exp = ([good.data_ptr()] + [None] * (n - 1)) * nseg
+    exp[-n] = bad.data_ptr()
+    a, b = (c_void_p * len(src))(*src), (c_void_p * len(exp))(*exp)
+    okbuf = torch.full((nseg + 2,), FILL, dtype=torch.uint8, device="cuda")
+    before = torch.cat(bufs)
+    enc = cess.New(k, m)
+    if rt_mode is not None:
+        enc.set_option(_lib.CEC_OPT_RT_MODE, rt_mode)
+    assert _lib.load().cec_verify_ptrs(enc._h, a, b, nseg, ln, okbuf[1:].data_ptr(), None) == 0
+    torch.cuda.synchronize()
+    ok = okbuf.cpu().numpy()
+    assert ok[0] == FILL and ok[-1] == FILL
+    assert (ok[1:-2] == 1).all() and ok[-2] == 0, np.flatnonzero(ok[1:-1] != 1)[:8]
+    assert torch.equal(before, torch.cat(bufs))
+
+
 @pytest.mark.parametrize("k,m", [(2, 1), (10, 4), (32, 32)])
 def test_agrees_with_verify_batch(torch, cess, corc, k, m):
     """The addresses of a batch, some of its segments corrupt, handed to cec_verify_ptrs: d_ok
