@@ -1865,7 +1865,8 @@ int cec_verify_batch(cec_codec* c, const uint8_t* d_data, const uint8_t* d_parit
   if (nseg == 0) return CEC_OK;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, hip_stream);
-  if (!c->force_generic) {  // RS(2,1): recompute and compare in one read-only pass
+  if (!c->force_generic) {  // RS(2,1), RS(32,32): recompute and compare in one read-only pass
+                            // where the layout fits (launch_verify_ct)
     Layout L = batch_layout(c, d_data, const_cast<uint8_t*>(d_parity), shard_len);
     HIP_TRY(hipMemsetAsync(d_ok, 1, nseg, st));
     if (cec::launch_verify_ct(c->k, c->m, L, d_ok, (uint32_t)nseg, st)) return check_launch();
