@@ -120,6 +120,8 @@ SIGNATURES = {
     "cec_hashq_add_resume": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t,
                                      c_size_t, c_size_t, c_void_p, c_void_p, c_size_t,
                                      POINTER(c_uint64)]),
+    "cec_hashq_add_ptrs": (c_int, [c_void_p, POINTER(c_void_p), c_size_t, c_size_t, c_void_p,
+                                   POINTER(c_uint64)]),
     "cec_hashq_tick": (c_int, [c_void_p, c_uint32]),
     "cec_hashq_finish": (c_int, [c_void_p]),
     "cec_hashq_status": (c_int, [c_void_p, c_uint64, POINTER(c_int), POINTER(c_size_t),
@@ -137,6 +139,9 @@ SIGNATURES = {
                                       POINTER(c_uint32), POINTER(c_size_t)]),
     "cec_audit_chunks": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_uint32,
                                  POINTER(c_uint32), c_uint32, c_void_p, c_void_p, c_void_p]),
+    "cec_audit_chunks_ptrs": (c_int, [c_void_p, POINTER(c_void_p), c_size_t, c_size_t, c_uint32,
+                                      POINTER(c_uint32), c_uint32, c_void_p, c_void_p,
+                                      c_void_p]),
     "cec_scale_compact": (c_int, [c_uint32, c_void_p, c_size_t, POINTER(c_size_t)]),
     "cec_scale_deal_info": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t,
                                     POINTER(c_size_t)]),

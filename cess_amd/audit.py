@@ -1,4 +1,5 @@
-"""Storage-audit chunks on HBM-resident fragment batches.
+"""Storage-audit chunks on HBM-resident fragment batches
+(`audit_chunks`) and on fragments that are separate device tensors (`audit_chunks_device`).
 
 Reference: a fragment is CHUNK_COUNT = 1024 chunks (primitives/common/src/lib.rs:62), so an 8 MiB
 fragment is 1024 chunks of 8 KiB. A challenge (`generation_challenge`,
@@ -11,13 +12,13 @@ are not in the reference (unpinned, not provided here).
 """
 from __future__ import annotations
 
-from ctypes import POINTER, byref, c_size_t, c_uint32, c_uint64
+from ctypes import POINTER, byref, c_size_t, c_uint32, c_uint64, c_void_p
 from typing import Optional, Sequence
 
 import numpy as np
 
 from . import _lib
-from .reedsolomon import Encoder, _dev_ptr, _stream_handle, check
+from .reedsolomon import (Encoder, ErrInvalidInput, _dev_ptr, _on_gpu, _stream_handle, check)
 
 CHUNK_COUNT = _lib.CEC_CHUNK_COUNT
 CHALLENGE_NEED = CHUNK_COUNT * 46 // 1000  # 47
@@ -70,3 +71,30 @@ def audit_chunks(enc: Encoder, d_data, d_parity, nseg: int, shard_len: int,
         shard_len, chunk_count, idx.ctypes.data_as(POINTER(c_uint32)), idx.size,
         None if d_chunks is None else _dev_ptr(d_chunks),
         None if d_hex is None else _dev_ptr(d_hex), _stream_handle(stream)), "audit_chunks")
+
+
+def audit_chunks_device(enc: Encoder, frags: Sequence, indices: Sequence[int], d_chunks=None,
+                        d_hex=None, chunk_count: int = CHUNK_COUNT, stream=None) -> None:
+    """audit_chunks for scattered fragments, in place (cec_audit_chunks_ptrs): `frags` is a
+    sequence of 1-D uint8 device tensors of one length, each in its own allocation (a miner holds
+    one fragment of many segments). Chunk indices[j] of frags[f] goes to d_chunks [nfrag][nidx]
+    [len / chunk_count] and/or its SHA-256 hex to d_hex [nfrag][nidx][64]. With d_chunks None the
+    chunks are hashed where they lie: no chunk byte is copied. An empty `frags` returns quietly;
+    a None entry raises ErrInvalidInput, tensors of different lengths ErrShardSize, empty ones
+    ErrShardNoData, before any C call. Enqueued on `stream` (default: torch's current stream) and
+    not waited for."""
+    frags = list(frags)
+    if not frags:
+        return
+    if any(t is None for t in frags):
+        raise ErrInvalidInput(ErrInvalidInput.__doc__)
+    size = enc._check_device_shards(frags)
+    import torch
+    dev = torch.device("cuda", enc.device)
+    ptrs = (c_void_p * len(frags))(*[_dev_ptr(_on_gpu(t, dev)) for t in frags])
+    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint32))
+    check(enc._lib.cec_audit_chunks_ptrs(
+        enc._h, ptrs, len(frags), size, chunk_count, idx.ctypes.data_as(POINTER(c_uint32)),
+        idx.size, None if d_chunks is None else _dev_ptr(d_chunks),
+        None if d_hex is None else _dev_ptr(d_hex), enc._device_stream(stream)),
+        "audit_chunks_device")

@@ -2254,6 +2254,74 @@ int cec_audit_chunks(cec_codec* c, const uint8_t* d_data, const uint8_t* d_parit
   return rc ? rc : mrc;
 }
 
+int cec_audit_chunks_ptrs(cec_codec* c, const uint8_t* const* frags, size_t nfrag,
+                          size_t shard_len, uint32_t chunk_count, const uint32_t* indices,
+                          uint32_t nidx, uint8_t* d_chunks, uint8_t* d_hex, void* hip_stream) {
+  if (!c || (!d_chunks && !d_hex)) return set_err(CEC_EINVAL, "null");
+  if (chunk_count == 0 || shard_len == 0 || shard_len % chunk_count)
+    return set_err(CEC_ESHARDLEN, "shard_len must be a nonzero multiple of chunk_count");
+  if (nfrag == 0 || nidx == 0) return CEC_OK;
+  if (!frags || !indices) return set_err(CEC_EINVAL, "null");
+  for (uint32_t j = 0; j < nidx; ++j)
+    if (indices[j] >= chunk_count) return set_err(CEC_EINVAL, "chunk index out of range");
+  const uint64_t chunk = shard_len / chunk_count;
+  uintptr_t bits = (uintptr_t)d_chunks | chunk;
+  for (size_t f = 0; f < nfrag; ++f) {
+    if (!frags[f]) return set_err(CEC_EINVAL, "null fragment");
+    if (frags[f] == d_chunks || frags[f] == d_hex)
+      return set_err(CEC_EINVAL, "an output is a fragment of the call");
+    bits |= (uintptr_t)frags[f];
+  }
+  // one chain index and one table word per chunk, both 32-bit counted in the kernels; grid x
+  if (nfrag > 0xFFFFFFFFull / nidx) return set_err(CEC_EINVAL, "too many chunks (>= 2^32)");
+  const bool vec_ok = (bits & 15) == 0;
+  const uint64_t per_tile = vec_ok ? 256 * 16 : 256;
+  if ((chunk + per_tile - 1) / per_tile * nidx > 0x7fffffffull)
+    return set_err(CEC_EINVAL, "nidx * chunk too large for one grid");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, hip_stream);
+  // Address tables only, in one pool block: the fragment addresses (8 bytes each), the indices
+  // (4 bytes each, padded to a word) and, for the hashes, one address per chunk, filled on the
+  // device. No chunk byte is copied for the hashes and nothing chunk-sized is allocated.
+  const size_t nchunks = nfrag * nidx;
+  const size_t idx_words = ((size_t)nidx + 1) / 2;
+  const size_t up_words = nfrag + idx_words;
+  const size_t bytes = (up_words + (d_hex ? nchunks : 0)) * sizeof(uint64_t);
+  std::vector<uint64_t> host(up_words, 0);
+  for (size_t f = 0; f < nfrag; ++f) host[f] = (uint64_t)(uintptr_t)frags[f];
+  std::memcpy(host.data() + nfrag, indices, nidx * sizeof(uint32_t));
+  void* d = nullptr;
+  int rc = c->pool.alloc(bytes, &d);
+  if (rc) return rc;
+  hipError_t e = hipMemcpyAsync(d, host.data(), up_words * sizeof(uint64_t),
+                                hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    c->pool.retire(d, bytes);
+    return set_err(CEC_EHIP, std::string("table upload: ") + hipGetErrorString(e));
+  }
+  const uint64_t* d_frags = static_cast<const uint64_t*>(d);
+  const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d_frags + nfrag);
+  uint64_t* d_addrs = static_cast<uint64_t*>(d) + up_words;
+  if (d_chunks) {
+    cec::launch_chunk_gather_tab(d_frags, nfrag, d_idx, nidx, chunk, d_chunks, vec_ok, st);
+    rc = check_launch();
+  }
+  if (!rc && d_hex) {
+    // hashed where they lie, also when the chunks are gathered: the same bytes either way
+    cec::launch_chunk_addrs(d_frags, nfrag, d_idx, nidx, chunk, d_addrs, st);
+    rc = check_launch();
+    if (!rc) {
+      cec::launch_sha256_hex(c->opts.sha_mode, reinterpret_cast<const uint8_t* const*>(d_addrs),
+                             nullptr, 1, nchunks, chunk, d_hex, st);
+      rc = check_launch();
+    }
+  }
+  const int mrc = c->pool.mark(st);  // the tables stay until these complete
+  c->pool.retire(d, bytes);
+  return rc ? rc : mrc;
+}
+
 // ---- host-buffer API -------------------------------------------------------------------
 
 int cec_encode(cec_codec* c, uint8_t* const* shards, size_t shard_len) {

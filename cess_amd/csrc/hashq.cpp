@@ -163,6 +163,36 @@ int cec_hashq_add(cec_hashq* q, const uint8_t* d_base, size_t n, size_t per, siz
                               hex_outer, 0, nullptr, 0, ticket);
 }
 
+int cec_hashq_add_ptrs(cec_hashq* q, const uint8_t* const* d_bufs, size_t n, size_t len,
+                       uint8_t* d_hex, uint64_t* ticket) {
+  if (!q || (n && !d_bufs)) return cec::set_error(CEC_EINVAL, "null");
+  if (n > 0xFFFFFFFFull) return cec::set_error(CEC_EINVAL, "n too large");
+  for (size_t i = 0; i < n; ++i)
+    if (!d_bufs[i]) return cec::set_error(CEC_EINVAL, "null buffer");
+  if (n == 0) {
+    if (ticket) *ticket = 0;
+    return CEC_OK;
+  }
+  if (q->tail + n - q->head > q->cap)
+    return cec::set_error(CEC_ENOMEM, "hash queue full: tick until chains complete");
+  HQ_TRY(hipSetDevice(q->device));
+  // the addresses go in the kernel arguments, kHashqAddPtrs per launch: the array is the
+  // caller's again on return and nothing waits for the ticks queued before. Slots past the tail
+  // are not live until the bookkeeping below, so a failed launch leaves the ring as it was.
+  for (size_t i0 = 0; i0 < n; i0 += cec::kHashqAddPtrs) {
+    const uint32_t cnt = (uint32_t)std::min<size_t>(cec::kHashqAddPtrs, n - i0);
+    cec::launch_hashq_add_ptrs(q->tab, q->cap - 1, q->tail + i0, cnt, d_bufs + i0, len,
+                               d_hex ? d_hex + 64 * i0 : nullptr, q->stream);
+    int rc = launched();
+    if (rc) return rc;
+  }
+  q->adds.push_back({q->tail, n, cec::sha256_blocks(len), 0, q->next_ticket});
+  q->tail += n;
+  if (ticket) *ticket = q->next_ticket;
+  ++q->next_ticket;
+  return CEC_OK;
+}
+
 int cec_hashq_tick(cec_hashq* q, uint32_t max_blocks) {
   if (!q) return cec::set_error(CEC_EINVAL, "null");
   if (q->adds.empty()) return CEC_OK;

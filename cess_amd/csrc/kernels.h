@@ -192,6 +192,12 @@ void launch_hashq_add(ShaChain* tab, uint32_t mask, uint64_t slot0, uint32_t n,
                       uint64_t len, uint8_t* hex, uint64_t hex_outer, uint64_t pre_blk,
                       uint8_t* pre_hex, uint64_t pre_hex_outer, hipStream_t st,
                       const uint32_t* h0 = nullptr, uint64_t blk0 = 0);
+// The same for n <= kHashqAddPtrs buffers at arbitrary device addresses (cec_hashq_add_ptrs):
+// chain i hashes the len bytes at src[i] (a HOST array, copied into the kernel arguments: a 2 KiB
+// block, under the 4 KiB limit) and writes its hex to hex + 64 * i (hex null: no output).
+constexpr uint32_t kHashqAddPtrs = 256;
+void launch_hashq_add_ptrs(ShaChain* tab, uint32_t mask, uint64_t slot0, uint32_t n,
+                           const uint8_t* const* src, uint64_t len, uint8_t* hex, hipStream_t st);
 // Advance the n chains in slots head.. by at most max_blocks blocks each; tick_mode 0 lets `live`
 // (chains not yet complete among them) pick the kernel form, 1 or 2 = two waves with that many
 // blocks prefetched, 3 = one wave per 64 chains.
@@ -202,6 +208,16 @@ void launch_sha256_tick(int tick_mode, ShaChain* tab, uint32_t mask, uint64_t he
 // batch order (f = seg * nshards + shard, shards of layout L), to out[(f * nidx + j) * chunk_len].
 void launch_chunk_gather(const Layout& L, int nshards, uint64_t nfrag, const uint32_t* d_idx,
                          uint32_t nidx, uint64_t chunk_len, uint8_t* out, hipStream_t st);
+// The same gather of scattered fragments (cec_audit_chunks_ptrs): fragment f is the bytes at
+// d_frags[f] (a device table of nfrag addresses). vec_ok: every fragment address, `out` and
+// chunk_len are 16-byte multiples (16-byte columns; else byte-wise for the whole launch).
+void launch_chunk_gather_tab(const uint64_t* d_frags, uint64_t nfrag, const uint32_t* d_idx,
+                             uint32_t nidx, uint64_t chunk_len, uint8_t* out, bool vec_ok,
+                             hipStream_t st);
+// d_addrs[f * nidx + j] = d_frags[f] + d_idx[j] * chunk_len (nfrag * nidx < 2^32 words): the
+// `ptrs` of launch_sha256_hex for hashing the challenged chunks in place.
+void launch_chunk_addrs(const uint64_t* d_frags, uint64_t nfrag, const uint32_t* d_idx,
+                        uint32_t nidx, uint64_t chunk_len, uint64_t* d_addrs, hipStream_t st);
 
 // XOR reduction (xor.hip): dst[0..len) ^= src[j * stride ..][0..len) for j < nsrc.
 void launch_xor_reduce(uint8_t* dst, const uint8_t* src, uint32_t nsrc, uint64_t stride,

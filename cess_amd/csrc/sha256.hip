@@ -1,6 +1,7 @@
 // SHA-256 kernels of libcessec (FIPS 180-4) for the fragment and segment hashes of CESS's
 // SegmentList (c-pallets/file-bank/src/types.rs:13-16): one-shot batch kernels (k_sha256,
-// k_sha256_2w) and the streaming hash-queue kernels (k_hashq_add, k_sha256_tick).
+// k_sha256_2w) and the streaming hash-queue kernels (k_hashq_add, k_hashq_add_ptrs,
+// k_sha256_tick).
 #include "dev_util.h"
 #include "kernels.h"
 
@@ -866,6 +867,45 @@ __global__ __launch_bounds__(256) void k_hashq_add(ShaChain* __restrict__ tab, u
   tab[(uint32_t)(slot0 + i) & mask] = c;
 }
 
+// The same for buffers at arbitrary addresses (cec_hashq_add_ptrs): the addresses travel in the
+// kernel arguments, so the add stays one small kernel with no host->device copy, no device table
+// to retire and no wait for the ticks already queued. The array is read through the kernarg
+// segment (constant address space) with the lane's index: a vector load from there, no private
+// copy of the 2 KiB block.
+struct HashqPtrArgs {
+  ShaChain* tab;
+  uint64_t slot0;
+  uint64_t len;
+  uint8_t* hex;
+  uint32_t mask, n;
+  const uint8_t* src[kHashqAddPtrs];
+};
+static_assert(sizeof(HashqPtrArgs) <= 2048 + 64, "a 2 KiB argument block plus the scalars");
+typedef const HashqPtrArgs __attribute__((address_space(4))) HashqPtrArgsK;
+
+__global__ __launch_bounds__(256) void k_hashq_add_ptrs(HashqPtrArgs a) {
+  const HashqPtrArgsK* __restrict__ K =
+      (const HashqPtrArgsK*)__builtin_amdgcn_kernarg_segment_ptr();  // the only argument: offset 0
+  const uint32_t i = threadIdx.x;
+  if (i >= a.n) return;
+  ShaChain c;
+  c.src = K->src[i];
+  c.len = a.len;
+  c.blk = 0;
+  c.hex = a.hex ? a.hex + (uint64_t)i * 64 : nullptr;
+  c.pre_blk = 0;
+  c.pre_hex = nullptr;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) c.pre_h[q] = 0;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) c.pad_[q] = 0;
+  const uint32_t iv[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a,
+                          0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+#pragma unroll
+  for (int q = 0; q < 8; ++q) c.h[q] = iv[q];
+  a.tab[(uint32_t)(a.slot0 + i) & a.mask] = c;
+}
+
 void launch_sha256_hex(int sha_mode, const uint8_t* const* ptrs, const Layout* L, int nshards,
                        uint64_t n, uint64_t len, uint8_t* hex_out, hipStream_t st) {
   if (n == 0) return;
@@ -895,6 +935,20 @@ void launch_hashq_add(ShaChain* tab, uint32_t mask, uint64_t slot0, uint32_t n,
   hipLaunchKernelGGL(k_hashq_add, dim3((n + 255) / 256), dim3(256), 0, st, tab, mask, slot0, n,
                      base, per, outer, inner, len, hex, hex_outer, pre_blk, pre_hex,
                      pre_hex_outer, h0, blk0);
+}
+
+void launch_hashq_add_ptrs(ShaChain* tab, uint32_t mask, uint64_t slot0, uint32_t n,
+                           const uint8_t* const* src, uint64_t len, uint8_t* hex, hipStream_t st) {
+  if (n == 0 || n > kHashqAddPtrs) return;
+  HashqPtrArgs a;
+  a.tab = tab;
+  a.slot0 = slot0;
+  a.len = len;
+  a.hex = hex;
+  a.mask = mask;
+  a.n = n;
+  for (uint32_t i = 0; i < kHashqAddPtrs; ++i) a.src[i] = i < n ? src[i] : nullptr;
+  hipLaunchKernelGGL(k_hashq_add_ptrs, dim3(1), dim3(256), 0, st, a);
 }
 
 // live chains below which the auto tick is the lane-pair form (three waves per 64 chains): at

@@ -19,7 +19,7 @@ from ctypes import byref, c_int, c_size_t, c_uint64, c_void_p
 from typing import Optional
 
 from . import _lib
-from .reedsolomon import _dev_ptr, _stream_handle, check
+from .reedsolomon import ErrShardSize, _dev_ptr, _stream_handle, check
 
 
 def sha256_blocks(length: int) -> int:
@@ -72,6 +72,26 @@ class HashQueue:
                                                prefix_len if prep else 0, prep,
                                                prefix_hex_outer, byref(t)),
               "HashQueue.add")
+        return t.value
+
+    def add_ptrs(self, tensors, d_hex=None, hex_offset: int = 0) -> int:
+        """Append one chain per tensor of `tensors`, 1-D uint8 device tensors of one length that
+        lie wherever the caller has them (cec_hashq_add_ptrs); chain i writes its hex at
+        d_hex + hex_offset + 64 * i (d_hex None: no output). The addresses travel in kernel
+        arguments: nothing is copied or waited for. A None entry is refused by the library
+        (CEC_EINVAL) with the ring unchanged; tensors of different lengths raise ErrShardSize.
+        Returns the add's ticket (0 for an empty sequence)."""
+        tensors = list(tensors)
+        n = len(tensors)
+        sizes = {t.numel() for t in tensors if t is not None}
+        if len(sizes) > 1:
+            raise ErrShardSize(ErrShardSize.__doc__)
+        length = sizes.pop() if sizes else 0
+        ptrs = (c_void_p * max(1, n))(*[None if t is None else _dev_ptr(t) for t in tensors])
+        t = c_uint64()
+        hexp = None if d_hex is None else _dev_ptr(d_hex) + hex_offset
+        check(_lib.load().cec_hashq_add_ptrs(self._h, ptrs, n, length, hexp, byref(t)),
+              "HashQueue.add_ptrs")
         return t.value
 
     def add_fragments(self, d_data, d_parity, nseg: int, k: int, m: int, shard_len: int,

@@ -92,8 +92,8 @@ int cec_verify(cec_codec* codec, uint8_t* const* shards, size_t shard_len, int* 
  * a decode program from the codec's cache, which may evict it while a graph still points at it:
  * do not capture those, nor cec_reconstruct_some_batch, nor the pointer-table calls
  * (cec_reconstruct_ptrs, cec_encode_ptrs, cec_verify_ptrs, cec_reconstruct_partial_ptrs,
- * cec_xor_ptrs, cec_encode_idx_ptrs, cec_update_ptrs: their kernels read a codec-owned table that is retired once the call's launches
- * complete). A single 16 MiB RS(2,1) segment's
+ * cec_xor_ptrs, cec_encode_idx_ptrs, cec_update_ptrs, cec_audit_chunks_ptrs: their kernels read a
+ * codec-owned table that is retired once the call's launches complete). A single 16 MiB RS(2,1) segment's
  * encode + three rebuilds: 29.5 us eagerly, 24.8 us as one graph (profiles/r05/graph_probe.log). */
 int cec_encode_batch(cec_codec* codec, const uint8_t* d_data, uint8_t* d_parity, size_t nseg,
                      size_t shard_len, void* hip_stream);
@@ -438,6 +438,18 @@ int cec_hashq_add_resume(cec_hashq* q, const uint8_t* d_base, size_t n, size_t p
                          size_t outer_stride, size_t inner_stride, size_t len, size_t start_len,
                          const uint32_t* d_states, uint8_t* d_hex, size_t hex_outer,
                          uint64_t* ticket);
+/* cec_hashq_add of n buffers at arbitrary device addresses: d_bufs is a HOST array of n DEVICE
+ * pointers of len bytes each (a rebuilt fragment in a caller-owned tensor, a miner's stored
+ * fragments scrubbed against their recorded hashes). Chain i writes its hex to d_hex + 64 * i
+ * (d_hex NULL: no output). The chains join the ring like those of cec_hashq_add: same ticks in
+ * every tick mode, same ticket and status bookkeeping; one add is one length. The addresses travel
+ * in kernel arguments (256 per launch), so there is no host->device copy, no table and no wait
+ * for the ticks already queued: the array belongs to the caller again on return. Checked before
+ * anything is enqueued (on an error the ring is unchanged): CEC_EINVAL for a NULL queue, a NULL
+ * array with n > 0, a NULL entry or n > 2^32 - 1; CEC_ENOMEM when the ring would overflow (nothing
+ * is added). n == 0: CEC_OK, ticket 0. */
+int cec_hashq_add_ptrs(cec_hashq* q, const uint8_t* const* d_bufs, size_t n, size_t len,
+                       uint8_t* d_hex, uint64_t* ticket);
 /* Advance every live chain by at most max_blocks 64-byte blocks (0 = to completion). */
 int cec_hashq_tick(cec_hashq* q, uint32_t max_blocks);
 /* Tick until every chain added so far is complete (enqueued; synchronise the stream to wait). */
@@ -573,6 +585,33 @@ int cec_audit_chunks(cec_codec* codec, const uint8_t* d_data, const uint8_t* d_p
                      size_t nseg, size_t shard_len, uint32_t chunk_count,
                      const uint32_t* indices, uint32_t nidx, uint8_t* d_chunks, uint8_t* d_hex,
                      void* hip_stream);
+/* The same audit of scattered fragments, in place: cec_audit_chunks without the batch. A miner that
+ * answers a challenge holds one fragment of many unrelated segments, each in its own allocation.
+ * frags: a HOST array of nfrag DEVICE pointers, each shard_len bytes. The outputs have the batch
+ * form's shape with the position in `frags` as the fragment index: d_chunks [nfrag][nidx][chunk],
+ * d_hex [nfrag][nidx][64], chunk = shard_len / chunk_count; either may be NULL (not both). The
+ * codec's geometry plays no part: the codec supplies the device, the pool and the default stream.
+ *  - Reads: only the nidx challenged chunks of each fragment. Fragments may alias each other:
+ *    they are only read. Writes: nothing but the named output bytes.
+ *  - Hashes: every chunk is hashed where it lies. With d_chunks NULL no chunk byte is copied and
+ *    nothing is allocated whose size grows with nfrag * nidx * chunk: the call takes address tables
+ *    only (8 bytes per fragment, 4 per index, 8 per chunk when d_hex is given). CEC_OPT_SHA_MODE
+ *    and its automatic choice apply as in cec_audit_chunks.
+ *  - Validation: everything is validated before anything is enqueued; on an error no byte is
+ *    written. CEC_EINVAL: a NULL codec; both outputs NULL; with work to do, a NULL frags or
+ *    indices, a NULL entry of frags, an index >= chunk_count, an output base equal to a fragment
+ *    address, or nfrag * nidx >= 2^32. CEC_ESHARDLEN: shard_len == 0, chunk_count == 0 or
+ *    shard_len % chunk_count != 0. nfrag == 0 or nidx == 0: CEC_OK, nothing done.
+ *  - Arrays: both host arrays belong to the caller again on return. The device tables come from
+ *    the codec's pool and are retired once the launches complete, as in cec_reconstruct_ptrs; the
+ *    work is enqueued on hip_stream and not waited for.
+ *  - Alignment: any alignment is correct. The gather takes 16-byte columns when every fragment
+ *    address, d_chunks and chunk are 16-byte multiples, otherwise the whole call runs byte-wise
+ *    (the fallback is per call).
+ *  - HIP graph capture: not capturable: the kernels read the codec-owned tables. */
+int cec_audit_chunks_ptrs(cec_codec* codec, const uint8_t* const* frags, size_t nfrag,
+                          size_t shard_len, uint32_t chunk_count, const uint32_t* indices,
+                          uint32_t nidx, uint8_t* d_chunks, uint8_t* d_hex, void* hip_stream);
 
 /* ---- multi-GPU degraded read over RCCL ----------------------------------------
  * One process (or thread) per GPU, each with its own codec. Fragment f of segment s is stored on

@@ -222,6 +222,8 @@ pub mod sys {
                                     d_hex: *mut u8, hex_outer: usize, prefix_len: usize,
                                     d_prefix_hex: *mut u8, prefix_hex_outer: usize,
                                     ticket: *mut u64) -> c_int;
+        pub fn cec_hashq_add_ptrs(q: *mut cec_hashq, d_bufs: *const *const u8, n: usize,
+                                  len: usize, d_hex: *mut u8, ticket: *mut u64) -> c_int;
         pub fn cec_hashq_tick(q: *mut cec_hashq, max_blocks: u32) -> c_int;
         pub fn cec_hashq_finish(q: *mut cec_hashq) -> c_int;
         pub fn cec_hashq_status(q: *const cec_hashq, ticket: u64, done: *mut c_int,
@@ -235,6 +237,10 @@ pub mod sys {
                                 nseg: usize, shard_len: usize, chunk_count: u32,
                                 indices: *const u32, nidx: u32, d_chunks: *mut u8,
                                 d_hex: *mut u8, stream: *mut c_void) -> c_int;
+        pub fn cec_audit_chunks_ptrs(c: *mut cec_codec, frags: *const *const u8, nfrag: usize,
+                                     shard_len: usize, chunk_count: u32, indices: *const u32,
+                                     nidx: u32, d_chunks: *mut u8, d_hex: *mut u8,
+                                     stream: *mut c_void) -> c_int;
         pub fn cec_scale_compact(n: u32, out: *mut u8, out_cap: usize, out_len: *mut usize)
                                  -> c_int;
         pub fn cec_scale_upload_declaration(file_hash_hex: *const u8, seg_hex: *const u8,
@@ -661,6 +667,30 @@ impl ReedSolomon {
                               old_data.len() / self.k, shard_len, stream))
     }
 
+    /// Storage-audit chunks of scattered device fragments in place (`cec_audit_chunks_ptrs`):
+    /// `frags` holds the device addresses of fragments of `shard_len` bytes, each `chunk_count`
+    /// chunks; chunk `indices[j]` of fragment f goes to `d_chunks[(f * nidx + j) * chunk ..]` and
+    /// its SHA-256 hex to `d_hex[(f * nidx + j) * 64 ..]` (either output may be null, not both).
+    /// With `d_chunks` null the chunks are hashed where they lie and no chunk byte is copied.
+    /// Enqueued on `stream` and not waited for; both slices may be reused as soon as the call
+    /// returns.
+    ///
+    /// # Safety
+    /// Every fragment address must be device memory of `shard_len` bytes, `d_chunks` of
+    /// `frags.len() * indices.len() * (shard_len / chunk_count)` and `d_hex` of
+    /// `frags.len() * indices.len() * 64` bytes, on the codec's GPU and valid until the stream has
+    /// passed the call's work; the outputs must not overlap a fragment.
+    pub unsafe fn audit_chunks_device(&self, frags: &[*const u8], shard_len: usize,
+                                      chunk_count: u32, indices: &[u32], d_chunks: *mut u8,
+                                      d_hex: *mut u8, stream: *mut c_void) -> Result<(), Error> {
+        if indices.len() > u32::MAX as usize {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        check(sys::cec_audit_chunks_ptrs(self.c, frags.as_ptr(), frags.len(), shard_len,
+                                         chunk_count, indices.as_ptr(), indices.len() as u32,
+                                         d_chunks, d_hex, stream))
+    }
+
     /// The decode rows of the `required` lost shards of pattern `present` (`cec_decode_rows`):
     /// (shard indices ascending, one row of k coefficients over `cec_survivors` each).
     pub fn decode_rows(&self, present: &[u8], required: &[u8]) -> Result<(Vec<u8>, Vec<u8>), Error> {
@@ -685,6 +715,21 @@ impl Drop for ReedSolomon {
     fn drop(&mut self) {
         unsafe { cec_destroy(self.c) }
     }
+}
+
+/// Append scattered device buffers to a hash queue (`cec_hashq_add_ptrs`): chain i hashes the
+/// `len` bytes at `d_bufs[i]` and writes its 64 hex chars to `d_hex + 64 * i` (null: no output).
+/// Returns the add's ticket (0 for an empty slice). The addresses travel in kernel arguments:
+/// nothing is copied or waited for, and the slice may be reused as soon as the call returns.
+///
+/// # Safety
+/// `q` must be a live queue; every address must be device memory of `len` bytes (`d_hex`:
+/// `64 * d_bufs.len()` bytes) on the queue's GPU that stays valid until the add is complete.
+pub unsafe fn hashq_add_ptrs(q: *mut sys::cec_hashq, d_bufs: &[*const u8], len: usize,
+                             d_hex: *mut u8) -> Result<u64, Error> {
+    let mut ticket = 0u64;
+    check(sys::cec_hashq_add_ptrs(q, d_bufs.as_ptr(), d_bufs.len(), len, d_hex, &mut ticket))?;
+    Ok(ticket)
 }
 
 /// One segment's SegmentList hashes: 64 hex chars for the segment, k+m for its fragments.
