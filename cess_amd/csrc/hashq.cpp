@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <deque>
 #include <string>
+#include <vector>
 
 #include "../../include/cess_ec.h"
 #include "kernels.h"
@@ -30,6 +31,10 @@ struct cec_hashq {
   uint64_t head = 0, tail = 0;  // absolute slot numbers; live slots are [head, tail)
   struct Add {
     uint64_t slot0, n, blocks, done, ticket;
+    // concat adds (cec_hashq_add_concat_ptrs): chains of `parts` buffers of part_blocks blocks
+    // each, the queue's copy of their n * parts addresses (chain-major). parts == 0: a plain add.
+    uint64_t parts = 0, part_blocks = 0;
+    std::vector<const uint8_t*> ptrs;
   };
   std::deque<Add> adds;  // adds not yet complete, in slot order
   uint64_t next_ticket = 1;
@@ -56,6 +61,28 @@ int launched() {
 void retire(cec_hashq* q) {
   while (!q->adds.empty() && q->adds.front().done == q->adds.front().blocks) q->adds.pop_front();
   q->head = q->adds.empty() ? q->tail : q->adds.front().slot0;
+}
+
+// Blocks until the chains of a concat add stand at the start of a part other than their first
+// (0: none ahead; the last part needs no boundary after it, its tail and the padding blocks are
+// read, or not read, by the ticks as for any chain).
+uint64_t to_boundary(const cec_hashq::Add& a) {
+  if (a.parts < 2 || a.done == a.blocks) return 0;
+  const uint64_t p = a.done / a.part_blocks + 1;
+  return p < a.parts ? p * a.part_blocks - a.done : 0;
+}
+
+// The chains of `a` stand at the start of part p: point them at it.
+int rebase(cec_hashq* q, const cec_hashq::Add& a, uint64_t p) {
+  for (uint64_t i0 = 0; i0 < a.n; i0 += cec::kHashqRebase) {
+    const uint32_t cnt = (uint32_t)std::min<uint64_t>(cec::kHashqRebase, a.n - i0);
+    cec::launch_hashq_rebase(q->tab, q->cap - 1, a.slot0 + i0, cnt,
+                             a.ptrs.data() + i0 * a.parts + p, (size_t)a.parts,
+                             p * a.part_blocks * 64, q->stream);
+    int rc = launched();
+    if (rc) return rc;
+  }
+  return CEC_OK;
 }
 
 }  // namespace
@@ -193,6 +220,64 @@ int cec_hashq_add_ptrs(cec_hashq* q, const uint8_t* const* d_bufs, size_t n, siz
   return CEC_OK;
 }
 
+int cec_hashq_add_concat_ptrs(cec_hashq* q, const uint8_t* const* d_parts, size_t n, size_t parts,
+                              size_t part_len, size_t len, uint8_t* d_hex, uint8_t* d_prefix_hex,
+                              uint64_t* ticket) {
+  if (!q || (n && !d_parts)) return cec::set_error(CEC_EINVAL, "null");
+  if (parts == 0) return cec::set_error(CEC_EINVAL, "parts == 0");
+  if (part_len == 0 || (part_len & 63))
+    return cec::set_error(CEC_EINVAL, "part_len must be a nonzero multiple of 64");
+  if (parts > ~(size_t)0 / part_len) return cec::set_error(CEC_EINVAL, "parts * part_len overflows");
+  if (len == 0) len = parts * part_len;
+  if (len <= (parts - 1) * part_len || len > parts * part_len)
+    return cec::set_error(CEC_EINVAL, "len must end inside the last part");
+  if (d_prefix_hex && len < part_len)
+    return cec::set_error(CEC_EINVAL, "the prefix digest needs a whole first part");
+  if (n > 0xFFFFFFFFull) return cec::set_error(CEC_EINVAL, "n too large");
+  if (n && parts > ~(size_t)0 / sizeof(void*) / n)
+    return cec::set_error(CEC_EINVAL, "n * parts overflows");
+  for (size_t i = 0; i < n * parts; ++i)
+    if (!d_parts[i]) return cec::set_error(CEC_EINVAL, "null buffer");
+  if (n == 0) {
+    if (ticket) *ticket = 0;
+    return CEC_OK;
+  }
+  if (q->tail + n - q->head > q->cap)
+    return cec::set_error(CEC_ENOMEM, "hash queue full: tick until chains complete");
+  // the queue's copy of the addresses: parts 1.. are needed when the chains get there, long
+  // after the caller has its array back (one part: nothing to move to, nothing kept)
+  std::vector<const uint8_t*> keep;
+  if (parts > 1) {
+    try {
+      keep.assign(d_parts, d_parts + n * parts);
+    } catch (const std::bad_alloc&) {
+      return cec::set_error(CEC_ENOMEM, "hashq concat addresses");
+    }
+  }
+  HQ_TRY(hipSetDevice(q->device));
+  // as cec_hashq_add_ptrs: the first parts' addresses in the kernel arguments, kHashqAddPtrs per
+  // launch; slots past the tail are not live until the bookkeeping below
+  for (size_t i0 = 0; i0 < n; i0 += cec::kHashqAddPtrs) {
+    const uint32_t cnt = (uint32_t)std::min<size_t>(cec::kHashqAddPtrs, n - i0);
+    cec::launch_hashq_add_concat(q->tab, q->cap - 1, q->tail + i0, cnt, d_parts + i0 * parts,
+                                 parts, len, d_hex ? d_hex + 64 * i0 : nullptr, part_len >> 6,
+                                 d_prefix_hex ? d_prefix_hex + 64 * i0 : nullptr, q->stream);
+    int rc = launched();
+    if (rc) return rc;
+  }
+  cec_hashq::Add a{q->tail, n, cec::sha256_blocks(len), 0, q->next_ticket};
+  if (parts > 1) {
+    a.parts = parts;
+    a.part_blocks = part_len >> 6;
+    a.ptrs = std::move(keep);
+  }
+  q->adds.push_back(std::move(a));
+  q->tail += n;
+  if (ticket) *ticket = q->next_ticket;
+  ++q->next_ticket;
+  return CEC_OK;
+}
+
 int cec_hashq_tick(cec_hashq* q, uint32_t max_blocks) {
   if (!q) return cec::set_error(CEC_EINVAL, "null");
   if (q->adds.empty()) return CEC_OK;
@@ -201,16 +286,33 @@ int cec_hashq_tick(cec_hashq* q, uint32_t max_blocks) {
     for (const auto& a : q->adds) most = std::max(most, a.blocks - a.done);
     max_blocks = (uint32_t)std::min<uint64_t>(most, 0xFFFFFFFFull);
   }
-  uint64_t live = 0;
-  for (const auto& a : q->adds)
-    if (a.done < a.blocks) live += a.n;
   HQ_TRY(hipSetDevice(q->device));
-  cec::launch_sha256_tick(q->tick_mode, q->tab, q->cap - 1, q->head, (uint32_t)(q->tail - q->head), max_blocks,
-                          live, q->stream);
-  int rc = launched();
-  if (rc) return rc;
-  for (auto& a : q->adds) a.done += std::min<uint64_t>(max_blocks, a.blocks - a.done);
-  retire(q);
+  // The tick kernels read a chain as flat src + blk * 64, so no launch may take a concat chain
+  // across a part boundary: the tick is cut at the nearest one over all live concat adds, the
+  // adds that then stand on a boundary are moved to their next part, and so on until max_blocks
+  // are issued. Every live chain of whatever kind advances by min(max_blocks, blocks left) in
+  // all; with no concat add live this is one launch.
+  for (uint64_t left = max_blocks; left && !q->adds.empty();) {
+    uint64_t live = 0, step = left;
+    for (const auto& a : q->adds) {
+      if (a.done < a.blocks) live += a.n;
+      if (const uint64_t b = to_boundary(a)) step = std::min(step, b);
+    }
+    cec::launch_sha256_tick(q->tick_mode, q->tab, q->cap - 1, q->head,
+                            (uint32_t)(q->tail - q->head), (uint32_t)step, live, q->stream);
+    int rc = launched();
+    if (rc) return rc;
+    for (auto& a : q->adds) {
+      const uint64_t adv = std::min<uint64_t>(step, a.blocks - a.done);
+      a.done += adv;
+      if (adv && a.parts > 1 && a.done % a.part_blocks == 0 && a.done / a.part_blocks < a.parts) {
+        rc = rebase(q, a, a.done / a.part_blocks);
+        if (rc) return rc;
+      }
+    }
+    left -= step;
+    retire(q);
+  }
   return CEC_OK;
 }
 

@@ -1,7 +1,7 @@
 // SHA-256 kernels of libcessec (FIPS 180-4) for the fragment and segment hashes of CESS's
 // SegmentList (c-pallets/file-bank/src/types.rs:13-16): one-shot batch kernels (k_sha256,
 // k_sha256_2w) and the streaming hash-queue kernels (k_hashq_add, k_hashq_add_ptrs,
-// k_sha256_tick).
+// k_hashq_add_concat, k_hashq_rebase, k_sha256_tick).
 #include "dev_util.h"
 #include "kernels.h"
 
@@ -906,6 +906,68 @@ __global__ __launch_bounds__(256) void k_hashq_add_ptrs(HashqPtrArgs a) {
   a.tab[(uint32_t)(a.slot0 + i) & a.mask] = c;
 }
 
+// Chains over several buffers back to back (cec_hashq_add_concat_ptrs). The add writes a chain
+// that starts in its first part: src = part 0, len = the whole chain, and the prefix digest after
+// part 0 when asked. The ticks address a chain as flat src + blk * 64, so the host never lets a
+// launch cross a part boundary and moves src between launches (k_hashq_rebase).
+struct HashqConcatArgs {
+  ShaChain* tab;
+  uint64_t slot0;
+  uint64_t len;
+  uint8_t* hex;
+  uint8_t* pre_hex;
+  uint64_t pre_blk;
+  uint32_t mask, n;
+  const uint8_t* src[kHashqAddPtrs];
+};
+static_assert(sizeof(HashqConcatArgs) <= 2048 + 64, "a 2 KiB argument block plus the scalars");
+typedef const HashqConcatArgs __attribute__((address_space(4))) HashqConcatArgsK;
+
+__global__ __launch_bounds__(256) void k_hashq_add_concat(HashqConcatArgs a) {
+  const HashqConcatArgsK* __restrict__ K =
+      (const HashqConcatArgsK*)__builtin_amdgcn_kernarg_segment_ptr();  // the only argument: offset 0
+  const uint32_t i = threadIdx.x;
+  if (i >= a.n) return;
+  ShaChain c;
+  c.src = K->src[i];
+  c.len = a.len;
+  c.blk = 0;
+  c.hex = a.hex ? a.hex + (uint64_t)i * 64 : nullptr;
+  c.pre_blk = a.pre_hex ? a.pre_blk : 0;
+  c.pre_hex = a.pre_hex ? a.pre_hex + (uint64_t)i * 64 : nullptr;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) c.pre_h[q] = 0;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) c.pad_[q] = 0;
+  const uint32_t iv[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a,
+                          0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+#pragma unroll
+  for (int q = 0; q < 8; ++q) c.h[q] = iv[q];
+  a.tab[(uint32_t)(a.slot0 + i) & a.mask] = c;
+}
+
+// Move n chains that stand at the start of their part p onto it: src = part address - off, where
+// off = p * part_len is the chain's byte position, so that src + blk * 64 lies inside the part for
+// every block of the part (and is dereferenced for no other). Integer arithmetic: the base itself
+// may point anywhere. off is a multiple of 64, so src keeps the part's own alignment.
+struct HashqRebaseArgs {
+  ShaChain* tab;
+  uint64_t slot0;
+  uint64_t off;
+  uint32_t mask, n;
+  uint64_t addr[kHashqRebase];
+};
+static_assert(sizeof(HashqRebaseArgs) <= 2048 + 64, "a 2 KiB argument block plus the scalars");
+typedef const HashqRebaseArgs __attribute__((address_space(4))) HashqRebaseArgsK;
+
+__global__ __launch_bounds__(256) void k_hashq_rebase(HashqRebaseArgs a) {
+  const HashqRebaseArgsK* __restrict__ K =
+      (const HashqRebaseArgsK*)__builtin_amdgcn_kernarg_segment_ptr();
+  const uint32_t i = threadIdx.x;
+  if (i >= a.n) return;
+  a.tab[(uint32_t)(a.slot0 + i) & a.mask].src = (const uint8_t*)(uintptr_t)(K->addr[i] - a.off);
+}
+
 void launch_sha256_hex(int sha_mode, const uint8_t* const* ptrs, const Layout* L, int nshards,
                        uint64_t n, uint64_t len, uint8_t* hex_out, hipStream_t st) {
   if (n == 0) return;
@@ -949,6 +1011,36 @@ void launch_hashq_add_ptrs(ShaChain* tab, uint32_t mask, uint64_t slot0, uint32_
   a.n = n;
   for (uint32_t i = 0; i < kHashqAddPtrs; ++i) a.src[i] = i < n ? src[i] : nullptr;
   hipLaunchKernelGGL(k_hashq_add_ptrs, dim3(1), dim3(256), 0, st, a);
+}
+
+void launch_hashq_add_concat(ShaChain* tab, uint32_t mask, uint64_t slot0, uint32_t n,
+                             const uint8_t* const* src, size_t stride, uint64_t len, uint8_t* hex,
+                             uint64_t pre_blk, uint8_t* pre_hex, hipStream_t st) {
+  if (n == 0 || n > kHashqAddPtrs) return;
+  HashqConcatArgs a;
+  a.tab = tab;
+  a.slot0 = slot0;
+  a.len = len;
+  a.hex = hex;
+  a.pre_hex = pre_hex;
+  a.pre_blk = pre_blk;
+  a.mask = mask;
+  a.n = n;
+  for (uint32_t i = 0; i < kHashqAddPtrs; ++i) a.src[i] = i < n ? src[i * stride] : nullptr;
+  hipLaunchKernelGGL(k_hashq_add_concat, dim3(1), dim3(256), 0, st, a);
+}
+
+void launch_hashq_rebase(ShaChain* tab, uint32_t mask, uint64_t slot0, uint32_t n,
+                         const uint8_t* const* addr, size_t stride, uint64_t off, hipStream_t st) {
+  if (n == 0 || n > kHashqRebase) return;
+  HashqRebaseArgs a;
+  a.tab = tab;
+  a.slot0 = slot0;
+  a.off = off;
+  a.mask = mask;
+  a.n = n;
+  for (uint32_t i = 0; i < kHashqRebase; ++i) a.addr[i] = i < n ? (uint64_t)(uintptr_t)addr[i * stride] : 0;
+  hipLaunchKernelGGL(k_hashq_rebase, dim3(1), dim3(256), 0, st, a);
 }
 
 // live chains below which the auto tick is the lane-pair form (three waves per 64 chains): at

@@ -19,7 +19,8 @@ from ctypes import byref, c_int, c_size_t, c_uint64, c_void_p
 from typing import Optional
 
 from . import _lib
-from .reedsolomon import ErrShardSize, _dev_ptr, _stream_handle, check
+from .reedsolomon import (CecError, ErrInvalidInput, ErrShardNoData, ErrShardSize, _dev_ptr,
+                          _stream_handle, check)
 
 
 def sha256_blocks(length: int) -> int:
@@ -94,6 +95,51 @@ class HashQueue:
               "HashQueue.add_ptrs")
         return t.value
 
+    def add_concat_ptrs(self, chains, d_hex=None, hex_offset: int = 0, d_prefix_hex=None,
+                        prefix_hex_offset: int = 0, length: Optional[int] = None) -> int:
+        """Append one chain per row of `chains`: a row is a sequence of 1-D uint8 device tensors of
+        one size (a multiple of 64) that lie wherever the caller has them, and its chain hashes
+        them back to back, in place (cec_hashq_add_concat_ptrs). `length` is the chain's total
+        byte count where the last tensor of a row counts only in part (None: all of it). Chain i
+        writes its hex at d_hex + hex_offset + 64 * i and, with d_prefix_hex, the hex of its first
+        tensor at d_prefix_hex + prefix_hex_offset + 64 * i. Rows of different lengths or tensors
+        of different sizes raise ErrShardSize, a None entry ErrInvalidInput, empty tensors
+        ErrShardNoData, before any C call; what the library refuses (a size that is no multiple
+        of 64, a `length` that does not end in the last tensor) raises ErrInvalidInput with the
+        ring unchanged. Returns the add's ticket (0 for an empty sequence, without a C call)."""
+        chains = [list(row) for row in chains]
+        n = len(chains)
+        if n == 0:
+            return 0
+        parts = len(chains[0])
+        if any(len(row) != parts for row in chains):
+            raise ErrShardSize(ErrShardSize.__doc__)
+        flat = [t for row in chains for t in row]
+        if any(t is None for t in flat):
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        sizes = {t.numel() for t in flat}
+        if len(sizes) > 1:
+            raise ErrShardSize(ErrShardSize.__doc__)
+        part_len = sizes.pop() if sizes else 0
+        if part_len == 0:
+            raise ErrShardNoData(ErrShardNoData.__doc__)
+        ptrs = (c_void_p * len(flat))(*[_dev_ptr(t) for t in flat])
+        t = c_uint64()
+        hexp = None if d_hex is None else _dev_ptr(d_hex) + hex_offset
+        prep = None if d_prefix_hex is None else _dev_ptr(d_prefix_hex) + prefix_hex_offset
+        try:
+            check(_lib.load().cec_hashq_add_concat_ptrs(self._h, ptrs, n, parts, part_len,
+                                                        0 if length is None else length, hexp,
+                                                        prep, byref(t)),
+                  "HashQueue.add_concat_ptrs")
+        except CecError as e:
+            if e.code != _lib.CEC_EINVAL or isinstance(e, ErrInvalidInput):
+                raise
+            bad = ErrInvalidInput(str(e))
+            bad.code = e.code
+            raise bad from None
+        return t.value
+
     def add_fragments(self, d_data, d_parity, nseg: int, k: int, m: int, shard_len: int,
                       d_hex, with_parity: bool = True) -> int:
         """Hash every fragment of a batch ([nseg][k][len] data, [nseg][m][len] parity) into
@@ -136,6 +182,40 @@ class HashQueue:
         if m:
             self.add(d_parity, nseg * m, m, m * shard_len, shard_len, shard_len, d_frag_hex,
                      n_sh, k * 64)
+        return t
+
+    def add_segment_lists_device(self, segments, k: int, m: int, d_seg_hex, d_frag_hex) -> int:
+        """add_segment_lists for shards that each lie in a tensor of their own, in place:
+        segments[s] holds the k + m 1-D uint8 device tensors of segment s (data then parity, one
+        size, a multiple of 64: else ErrShardSize). Segment hashes go into d_seg_hex[nseg][64],
+        fragment hashes into d_frag_hex[nseg][k+m][64]. Per segment, a concat add runs the segment's
+        chain over its k data shards and yields data fragment 0's hash as its prefix digest, and
+        an add_ptrs hashes fragments 1..k+m-1. Nothing is copied. Returns the ticket of the last
+        segment chain: the segment chains are the longest and complete in the same tick (0 for
+        no segments)."""
+        segments = [list(seg) for seg in segments]
+        n_sh = k + m
+        if any(len(seg) != n_sh for seg in segments):
+            raise ErrShardSize(ErrShardSize.__doc__)
+        if not segments:
+            return 0
+        flat = [t for seg in segments for t in seg]
+        if any(t is None for t in flat):
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        sizes = {t.numel() for t in flat}
+        if len(sizes) > 1 or next(iter(sizes)) % 64:
+            raise ErrShardSize(ErrShardSize.__doc__)
+        if 0 in sizes:
+            raise ErrShardNoData(ErrShardNoData.__doc__)
+        # the C calls lay their hex out 64 bytes apart, a segment's fragment slots lie in its own
+        # row of d_frag_hex: so one concat add and one pointer add per segment, a few small
+        # launches each. The chains of all segments stand at the same block, so their part
+        # boundaries cut a tick once, not once per segment.
+        t = 0
+        for s, seg in enumerate(segments):
+            if n_sh > 1:
+                self.add_ptrs(seg[1:], d_frag_hex, (s * n_sh + 1) * 64)
+            t = self.add_concat_ptrs([seg[:k]], d_seg_hex, s * 64, d_frag_hex, s * n_sh * 64)
         return t
 
     def set_option(self, option: int, value: int) -> None:

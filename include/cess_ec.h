@@ -450,6 +450,28 @@ int cec_hashq_add_resume(cec_hashq* q, const uint8_t* d_base, size_t n, size_t p
  * is added). n == 0: CEC_OK, ticket 0. */
 int cec_hashq_add_ptrs(cec_hashq* q, const uint8_t* const* d_bufs, size_t n, size_t len,
                        uint8_t* d_hex, uint64_t* ticket);
+/* cec_hashq_add_ptrs of chains that each run over several buffers back to back (a segment whose
+ * data fragments lie in separate tensors, a file digest over scattered segments): d_parts is a
+ * HOST array of n * parts DEVICE pointers, chain i hashes the concatenation of
+ * d_parts[i * parts + 0 .. parts). Every part is part_len bytes (a nonzero multiple of 64, so no
+ * SHA block straddles two parts) except that the last contributes len - (parts - 1) * part_len:
+ * len is the chain's total length, (parts - 1) * part_len < len <= parts * part_len, 0 meaning
+ * parts * part_len. Reads only those bytes, in place. Chain i writes its hex to d_hex + 64 * i
+ * (NULL: no output) and, with d_prefix_hex, the hex of its first part (the prefix digest of
+ * cec_hashq_add_prefix at part_len: data fragment 0's hash; needs len >= part_len) to
+ * d_prefix_hex + 64 * i. The chains join the ring like those of any add: same ticket and status
+ * bookkeeping, every tick mode; a tick that would carry such a chain from one part into the next
+ * is issued as one launch up to the boundary, a small launch that moves the chain onto its next
+ * part, and one launch for the rest, every live chain still advancing by min(max_blocks, blocks
+ * left) per cec_hashq_tick. The array belongs to the caller again on return: the first parts'
+ * addresses travel in kernel arguments (256 per launch), the queue keeps a host copy of the array
+ * while the add is live. Checked before anything is enqueued (on an error the ring is unchanged):
+ * CEC_EINVAL for a NULL queue, a NULL array with n > 0, a NULL entry, parts == 0, part_len zero or
+ * not a multiple of 64, len outside its range or n > 2^32 - 1; CEC_ENOMEM when the ring would
+ * overflow (nothing is added). n == 0: CEC_OK, ticket 0. parts == 1 is cec_hashq_add_ptrs. */
+int cec_hashq_add_concat_ptrs(cec_hashq* q, const uint8_t* const* d_parts, size_t n, size_t parts,
+                              size_t part_len, size_t len, uint8_t* d_hex, uint8_t* d_prefix_hex,
+                              uint64_t* ticket);
 /* Advance every live chain by at most max_blocks 64-byte blocks (0 = to completion). */
 int cec_hashq_tick(cec_hashq* q, uint32_t max_blocks);
 /* Tick until every chain added so far is complete (enqueued; synchronise the stream to wait). */

@@ -224,6 +224,10 @@ pub mod sys {
                                     ticket: *mut u64) -> c_int;
         pub fn cec_hashq_add_ptrs(q: *mut cec_hashq, d_bufs: *const *const u8, n: usize,
                                   len: usize, d_hex: *mut u8, ticket: *mut u64) -> c_int;
+        pub fn cec_hashq_add_concat_ptrs(q: *mut cec_hashq, d_parts: *const *const u8, n: usize,
+                                         parts: usize, part_len: usize, len: usize,
+                                         d_hex: *mut u8, d_prefix_hex: *mut u8,
+                                         ticket: *mut u64) -> c_int;
         pub fn cec_hashq_tick(q: *mut cec_hashq, max_blocks: u32) -> c_int;
         pub fn cec_hashq_finish(q: *mut cec_hashq) -> c_int;
         pub fn cec_hashq_status(q: *const cec_hashq, ticket: u64, done: *mut c_int,
@@ -729,6 +733,31 @@ pub unsafe fn hashq_add_ptrs(q: *mut sys::cec_hashq, d_bufs: &[*const u8], len: 
                              d_hex: *mut u8) -> Result<u64, Error> {
     let mut ticket = 0u64;
     check(sys::cec_hashq_add_ptrs(q, d_bufs.as_ptr(), d_bufs.len(), len, d_hex, &mut ticket))?;
+    Ok(ticket)
+}
+
+/// Append chains that each run over several scattered device buffers back to back
+/// (`cec_hashq_add_concat_ptrs`): `d_parts` holds `parts` addresses per chain, chain-major; chain
+/// i hashes its parts in order, `part_len` bytes each (a nonzero multiple of 64), the last one
+/// only as far as the chain's total `len` (0: all of it). It writes its 64 hex chars to
+/// `d_hex + 64 * i` and, unless `d_prefix_hex` is null, those of its first part to
+/// `d_prefix_hex + 64 * i` (null: no output). Returns the add's ticket (0 for an empty slice).
+/// Nothing is copied on the device; the queue keeps its own copy of the addresses, so the slice
+/// may be reused as soon as the call returns.
+///
+/// # Safety
+/// `q` must be a live queue; `d_parts.len()` must be a multiple of `parts`; every address must be
+/// device memory of `part_len` bytes (`d_hex`, `d_prefix_hex`: 64 bytes per chain) on the queue's
+/// GPU that stays valid until the add is complete.
+pub unsafe fn hashq_add_concat_ptrs(q: *mut sys::cec_hashq, d_parts: &[*const u8], parts: usize,
+                                    part_len: usize, len: usize, d_hex: *mut u8,
+                                    d_prefix_hex: *mut u8) -> Result<u64, Error> {
+    if parts == 0 || d_parts.len() % parts != 0 {
+        return Err(Error::from_code(CEC_EINVAL));
+    }
+    let mut ticket = 0u64;
+    check(sys::cec_hashq_add_concat_ptrs(q, d_parts.as_ptr(), d_parts.len() / parts, parts,
+                                         part_len, len, d_hex, d_prefix_hex, &mut ticket))?;
     Ok(ticket)
 }
 
