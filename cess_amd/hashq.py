@@ -75,6 +75,24 @@ class HashQueue:
               "HashQueue.add")
         return t.value
 
+    def add_resume(self, d_base, n: int, per: int, outer_stride: int, inner_stride: int,
+                   length: int, start_len: int, d_states, d_hex=None, hex_outer: int = 0,
+                   hex_offset: int = 0) -> int:
+        """`add` of n chains that resume after their first start_len bytes (a multiple of 64
+        within length's full blocks; cec_hashq_add_resume): chain i starts from the eight 32-bit
+        state words d_states[8 i .. 8 i + 7] (a device tensor, or the int address of memory the
+        device reads, such as a pinned host tensor's data_ptr(); as cec_sha256_host_state gives
+        them) and hashes bytes start_len .. length of its buffer. The states are read by the
+        add's kernel on the queue's stream. Returns the add's ticket (0 for n == 0)."""
+        t = c_uint64()
+        hexp = None if d_hex is None else _dev_ptr(d_hex) + hex_offset
+        states = None if d_states is None else _dev_ptr(d_states)
+        check(_lib.load().cec_hashq_add_resume(self._h, _dev_ptr(d_base), n, per, outer_stride,
+                                               inner_stride, length, start_len, states, hexp,
+                                               hex_outer, byref(t)),
+              "HashQueue.add_resume")
+        return t.value
+
     def add_ptrs(self, tensors, d_hex=None, hex_offset: int = 0) -> int:
         """Append one chain per tensor of `tensors`, 1-D uint8 device tensors of one length that
         lie wherever the caller has them (cec_hashq_add_ptrs); chain i writes its hex at
