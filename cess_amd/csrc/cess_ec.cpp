@@ -32,10 +32,12 @@
 #include "fftdec_cost.h"
 #include "fftdec_plan.h"
 #include "gf256.h"
+#include "host_util.h"
 #include "kernels.h"
 
 namespace {
 
+using cec::check_launch;
 using cec::KernelOpts;
 using cec::Layout;
 using BigMat = cec::Mat<cec::kMaxShards, cec::kMaxShards>;
@@ -48,14 +50,6 @@ int set_err(int code, const std::string& msg) {
   g_last_error = msg;
   return code;
 }
-
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess)                                                               \
-      return set_err(_e == hipErrorOutOfMemory ? CEC_ENOMEM : CEC_EHIP,                 \
-                     std::string(#expr) + ": " + hipGetErrorString(_e));                \
-  } while (0)
 
 // ---- device block pool with stream-ordered retirement -------------------------------------
 // Blocks come from the stream-ordered allocator on the codec's private stream and go back to it
@@ -76,8 +70,8 @@ class DevPool {
       return CEC_OK;
     }
     // complete before any stream uses it (a rare host wait: freed blocks are reused)
-    HIP_TRY(hipMallocAsync(out, (size_t)1 << c, st_));
-    HIP_TRY(hipStreamSynchronize(st_));
+    CEC_HIP_TRY(hipMallocAsync(out, (size_t)1 << c, st_));
+    CEC_HIP_TRY(hipStreamSynchronize(st_));
     held_ += (size_t)1 << c;
     return CEC_OK;
   }
@@ -92,7 +86,7 @@ class DevPool {
       ev = evpool_.back();
       evpool_.pop_back();
     } else {
-      HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      CEC_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
     hipError_t e = hipEventRecord(ev, st);
     if (e != hipSuccess) {
@@ -380,7 +374,7 @@ int build_program(DevPool& pool, hipStream_t upload, const uint8_t* in_idx, int 
     if (rc) return rc;  // prog's deleter retires the chunks built so far
     c.dev = static_cast<uint32_t*>(d);
     prog->chunks.push_back(c);
-    HIP_TRY(hipMemcpyAsync(c.dev, h, c.bytes, hipMemcpyHostToDevice, upload));
+    CEC_HIP_TRY(hipMemcpyAsync(c.dev, h, c.bytes, hipMemcpyHostToDevice, upload));
   }
   // the FFT-domain decode plans of the same pattern
   auto upload_plan = [&](const cec::FftDecPlan& fp, uint32_t** dev, size_t* dbytes) -> int {
@@ -398,7 +392,7 @@ int build_program(DevPool& pool, hipStream_t upload, const uint8_t* in_idx, int 
     if (rc) return rc;
     *dev = static_cast<uint32_t*>(d);
     *dbytes = bytes;
-    HIP_TRY(hipMemcpyAsync(*dev, h, bytes, hipMemcpyHostToDevice, upload));
+    CEC_HIP_TRY(hipMemcpyAsync(*dev, h, bytes, hipMemcpyHostToDevice, upload));
     return CEC_OK;
   };
   if (fdp) {
@@ -414,7 +408,7 @@ int build_program(DevPool& pool, hipStream_t upload, const uint8_t* in_idx, int 
   // the block may be a reused one whose readers have completed; the upload must land before
   // any caller-stream launch that reads it, and pageable images die here (arena images live
   // until the caller's synchronisation)
-  if (!staged) HIP_TRY(hipStreamSynchronize(upload));
+  if (!staged) CEC_HIP_TRY(hipStreamSynchronize(upload));
   *out = std::move(prog);
   return CEC_OK;
 }
@@ -557,12 +551,6 @@ void run_program(const KernelOpts& o, const Program& p, const Layout& L, const u
     launch_chunk(o, L, c.dev, nullptr, c.nin, c.nob, seg_list, nseg, st);
 }
 
-int check_launch() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_err(CEC_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  return CEC_OK;
-}
-
 int do_encode(cec_codec* c, const Layout& L, const uint32_t* seg_list, uint32_t nseg,
               hipStream_t st) {
   if (nseg == 0 || L.len == 0) return CEC_OK;
@@ -580,7 +568,7 @@ int scratch_alloc(cec_codec* c, size_t bytes, hipStream_t st, Scratch* s) {
   s->bytes = bytes;
   if (bytes >= kBigScratch) {
     s->async = true;
-    HIP_TRY(hipMallocAsync(&s->p, bytes, st));
+    CEC_HIP_TRY(hipMallocAsync(&s->p, bytes, st));
     return CEC_OK;
   }
   return c->pool.alloc(bytes, &s->p);
@@ -892,7 +880,7 @@ int ensure(uint8_t** buf, size_t* have, size_t need, hipStream_t st) {
   if (*buf) (void)hipFreeAsync(*buf, st);
   *buf = nullptr;
   *have = 0;
-  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(buf), need, st));
+  CEC_HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(buf), need, st));
   *have = need;
   return CEC_OK;
 }
@@ -921,12 +909,14 @@ int stage_ensure(cec_codec* c, size_t nshards, size_t len) {
 }
 int stage_up(cec_codec* c, uint8_t* dev, const uint8_t* const* host, int count, size_t len) {
   for (int i = 0; i < count; ++i)
-    HIP_TRY(hipMemcpyAsync(dev + i * pad256(len), host[i], len, hipMemcpyHostToDevice, c->stream));
+    CEC_HIP_TRY(hipMemcpyAsync(dev + i * pad256(len), host[i], len, hipMemcpyHostToDevice,
+                               c->stream));
   return CEC_OK;
 }
 int stage_down(cec_codec* c, uint8_t* const* host, const uint8_t* dev, int count, size_t len) {
   for (int i = 0; i < count; ++i)
-    HIP_TRY(hipMemcpyAsync(host[i], dev + i * pad256(len), len, hipMemcpyDeviceToHost, c->stream));
+    CEC_HIP_TRY(hipMemcpyAsync(host[i], dev + i * pad256(len), len, hipMemcpyDeviceToHost,
+                               c->stream));
   return CEC_OK;
 }
 
@@ -1233,7 +1223,7 @@ int cec_create(int k, int m, int device, cec_codec** out) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     return set_err(CEC_ENODEV, "no HIP device visible");
   if (device < 0 || device >= ndev) return set_err(CEC_EINVAL, "device index out of range");
-  HIP_TRY(hipSetDevice(device));
+  CEC_HIP_TRY(hipSetDevice(device));
   std::unique_ptr<cec_codec> c(new (std::nothrow) cec_codec);
   if (!c) return set_err(CEC_ENOMEM, "codec");
   c->k = k;
@@ -1247,7 +1237,7 @@ int cec_create(int k, int m, int device, cec_codec** out) {
     if (!cec::gf_encode_matrix(k, m, *c->E, *top, *topinv, *work))
       return set_err(CEC_EINVAL, "singular Vandermonde top block");
   }
-  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  CEC_HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   c->pool.set_stream(c->stream);
   {
     auto par = std::make_unique<BigMat>();
@@ -1336,7 +1326,7 @@ int cec_encode_batch(cec_codec* c, const uint8_t* d_data, uint8_t* d_parity, siz
                      size_t shard_len, void* hip_stream) {
   if (!c || (nseg && (!d_data || !d_parity))) return set_err(CEC_EINVAL, "null");
   if (int rc = check_batch(nseg, shard_len)) return rc;
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   Layout L = batch_layout(c, d_data, d_parity, shard_len);
   return do_encode(c, L, nullptr, (uint32_t)nseg, pick_stream(c, hip_stream));
 }
@@ -1350,7 +1340,7 @@ static int reconstruct_batch_impl(cec_codec* c, uint8_t* d_data, uint8_t* d_pari
   if (!c || !present || (nseg && (!d_data || !d_parity))) return set_err(CEC_EINVAL, "null");
   int rc = check_batch(nseg, shard_len);
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, hip_stream);
   const int n = c->k + c->m;
   Layout L = batch_layout(c, d_data, d_parity, shard_len);
@@ -1744,7 +1734,7 @@ int cec_reconstruct_ptrs(cec_codec* c, const uint8_t* const* src, uint8_t* const
   if (!c || (nseg && (!src || !dst))) return set_err(CEC_EINVAL, "null");
   if (int rc = check_batch(nseg, shard_len)) return rc;
   if (nseg == 0) return CEC_OK;
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   return reconstruct_ptrs_impl(c, src, dst, nseg, shard_len, pick_stream(c, hip_stream));
 }
 
@@ -1763,7 +1753,7 @@ int cec_encode_ptrs(cec_codec* c, const uint8_t* const* d_data_ptrs, uint8_t* co
       if (!(dst[s * n + c->k + o] = d_parity_ptrs[s * c->m + o]))
         return set_err(CEC_EINVAL, "null shard");
   }
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   return reconstruct_ptrs_impl(c, src.data(), dst.data(), nseg, shard_len,
                                pick_stream(c, hip_stream));
 }
@@ -1773,7 +1763,7 @@ int cec_verify_ptrs(cec_codec* c, const uint8_t* const* src, const uint8_t* cons
   if (!c || (nseg && (!src || !expect || !d_ok))) return set_err(CEC_EINVAL, "null");
   if (int rc = check_batch(nseg, shard_len)) return rc;
   if (nseg == 0) return CEC_OK;
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   // the expectations sit where a rebuild's destinations do; the compare kernels only read them
   return reconstruct_ptrs_impl(c, src, const_cast<uint8_t* const*>(expect), nseg, shard_len,
                                pick_stream(c, hip_stream), d_ok);
@@ -1785,7 +1775,7 @@ int cec_reconstruct_partial_ptrs(cec_codec* c, const uint8_t* const* src, uint8_
   if (!c || (nseg && (!src || !dst || !present))) return set_err(CEC_EINVAL, "null");
   if (int rc = check_batch(nseg, shard_len)) return rc;
   if (nseg == 0) return CEC_OK;
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   return partial_ptrs_impl(c, src, dst, present, nseg, shard_len, accumulate != 0,
                            pick_stream(c, hip_stream));
 }
@@ -1824,7 +1814,7 @@ int cec_xor_ptrs(cec_codec* c, uint8_t* const* dst, const uint8_t* const* src, s
     }
   }
   if (l.rows.empty()) return CEC_OK;
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, hip_stream);
   const bool vec_ok = (bits & 15) == 0;
   Uploads up{c->stream, c->arena};
@@ -1841,7 +1831,7 @@ int cec_reconstruct_partial_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_pari
     return set_err(CEC_EINVAL, "null");
   if (int rc = check_batch(nseg, shard_len)) return rc;
   if (nseg == 0) return CEC_OK;
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, hip_stream);
   const int n = c->k + c->m;
   Layout L = batch_layout(c, d_data, d_parity, shard_len);
@@ -1863,12 +1853,12 @@ int cec_verify_batch(cec_codec* c, const uint8_t* d_data, const uint8_t* d_parit
   if (!c || !d_ok || (nseg && (!d_data || !d_parity))) return set_err(CEC_EINVAL, "null");
   if (int rc = check_batch(nseg, shard_len)) return rc;
   if (nseg == 0) return CEC_OK;
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, hip_stream);
   if (!c->force_generic) {  // RS(2,1), RS(32,32): recompute and compare in one read-only pass
                             // where the layout fits (launch_verify_ct)
     Layout L = batch_layout(c, d_data, const_cast<uint8_t*>(d_parity), shard_len);
-    HIP_TRY(hipMemsetAsync(d_ok, 1, nseg, st));
+    CEC_HIP_TRY(hipMemsetAsync(d_ok, 1, nseg, st));
     if (cec::launch_verify_ct(c->k, c->m, L, d_ok, (uint32_t)nseg, st)) return check_launch();
   }
   // the parity recomputed into a scratch batch (the encode kernels: FFT for RS(32,32)), then
@@ -1952,7 +1942,7 @@ int cec_encode_idx_batch(cec_codec* c, const uint8_t* d_shard, size_t shard_seg_
   if (reads_meet(d_shard, shard_seg_stride, nseg, shard_len, d_parity,
                  nseg * (size_t)c->m * shard_len))
     return set_err(CEC_EINVAL, "the shard overlaps the parity");
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   uint8_t coef[cec::kMaxShards];
   parity_column(c, idx, coef);
   const uint32_t slot = 0;
@@ -1977,7 +1967,7 @@ int cec_update_batch(cec_codec* c, const uint8_t* d_old, const uint8_t* d_new, u
     if (reads_meet(d_old + j * shard_len, seg_stride, nseg, shard_len, d_parity, par_bytes) ||
         reads_meet(d_new + j * shard_len, seg_stride, nseg, shard_len, d_parity, par_bytes))
       return set_err(CEC_EINVAL, "a changed shard overlaps the parity");
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   std::vector<uint8_t> coef(slots.size() * c->m);
   for (size_t i = 0; i < slots.size(); ++i) parity_column(c, (int)slots[i], &coef[i * c->m]);
   cec::launch_acc(d_old, d_new, seg_stride, shard_len, d_parity, (uint64_t)c->m * shard_len,
@@ -2081,7 +2071,7 @@ static int acc_ptrs_impl(cec_codec* c, const uint8_t* const* in_a, const uint8_t
       }
     }
   }
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, hip_stream);
   Uploads up{c->stream, c->arena};
   int rc = run_ptr_table(c, launches, up, st, [] { return (int)CEC_OK; },
@@ -2112,7 +2102,7 @@ int cec_update_ptrs(cec_codec* c, const uint8_t* const* old_data, const uint8_t*
 int cec_sha256_batch(cec_codec* c, const uint8_t* d_data, const uint8_t* d_parity, size_t nseg,
                      size_t shard_len, uint8_t* d_hex, void* hip_stream) {
   if (!c || !d_hex || (nseg && !d_data)) return set_err(CEC_EINVAL, "null");
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   Layout L = batch_layout(c, d_data, d_parity, shard_len);
   int nsh = c->k + c->m;
   if (!d_parity) {
@@ -2132,7 +2122,7 @@ int cec_sha256_hex(const uint8_t* const* d_bufs, size_t n, size_t len, uint8_t* 
   const uint8_t** dptrs = nullptr;
   uint8_t* dhex = nullptr;
   // stream-ordered (hipFree would synchronise the whole device)
-  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&dptrs), n * sizeof(void*), st));
+  CEC_HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&dptrs), n * sizeof(void*), st));
   hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&dhex), n * 64, st);
   if (e != hipSuccess) {
     (void)hipFreeAsync(dptrs, st);
@@ -2209,7 +2199,7 @@ int cec_audit_chunks(cec_codec* c, const uint8_t* d_data, const uint8_t* d_parit
   for (uint32_t j = 0; j < nidx; ++j)
     if (indices[j] >= chunk_count) return set_err(CEC_EINVAL, "chunk index out of range");
   if (nseg == 0 || nidx == 0) return CEC_OK;
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, hip_stream);
   const int nsh = d_parity ? c->k + c->m : c->k;
   const uint64_t nfrag = (uint64_t)nseg * nsh;
@@ -2278,7 +2268,7 @@ int cec_audit_chunks_ptrs(cec_codec* c, const uint8_t* const* frags, size_t nfra
   const uint64_t per_tile = vec_ok ? 256 * 16 : 256;
   if ((chunk + per_tile - 1) / per_tile * nidx > 0x7fffffffull)
     return set_err(CEC_EINVAL, "nidx * chunk too large for one grid");
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, hip_stream);
   // Address tables only, in one pool block: the fragment addresses (8 bytes each), the indices
   // (4 bytes each, padded to a word) and, for the hashes, one address per chunk, filled on the
@@ -2330,7 +2320,7 @@ int cec_encode(cec_codec* c, uint8_t* const* shards, size_t shard_len) {
   const int n = c->k + c->m;
   for (int i = 0; i < n; ++i)
     if (!shards[i]) return set_err(CEC_EINVAL, "null shard");
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   int rc = stage_ensure(c, n, shard_len);
   if (rc) return rc;
   Layout L = stage_layout(c, shard_len);
@@ -2338,7 +2328,7 @@ int cec_encode(cec_codec* c, uint8_t* const* shards, size_t shard_len) {
   rc = do_encode(c, L, nullptr, 1, c->stream);
   if (rc) return rc;
   if ((rc = stage_down(c, shards + c->k, L.parity, c->m, shard_len))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  CEC_HIP_TRY(hipStreamSynchronize(c->stream));
   return CEC_OK;
 }
 
@@ -2347,7 +2337,7 @@ int cec_reconstruct(cec_codec* c, uint8_t* const* shards, const uint8_t* present
   if (!c || !shards || !present) return set_err(CEC_EINVAL, "null");
   if (int rc = check_batch(1, shard_len)) return rc;
   const int n = c->k + c->m;
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   ProgPtr p;
   int rc = get_decode(c, present, data_only != 0, &p);
   if (rc) return rc;
@@ -2369,7 +2359,7 @@ int cec_reconstruct(cec_codec* c, uint8_t* const* shards, const uint8_t* present
     const int i = p->out_idx[o];
     if ((rc = stage_down(c, shards + i, c->stage + i * stride, 1, shard_len))) return rc;
   }
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  CEC_HIP_TRY(hipStreamSynchronize(c->stream));
   evict_decode(c);  // the launch above has completed
   return CEC_OK;
 }
@@ -2380,7 +2370,7 @@ int cec_verify(cec_codec* c, uint8_t* const* shards, size_t shard_len, int* ok) 
   const int n = c->k + c->m;
   for (int i = 0; i < n; ++i)
     if (!shards[i]) return set_err(CEC_EINVAL, "null shard");
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   int rc = stage_ensure(c, n, shard_len);
   if (rc) return rc;
   Layout L = stage_layout(c, shard_len);
@@ -2392,7 +2382,7 @@ int cec_verify(cec_codec* c, uint8_t* const* shards, size_t shard_len, int* ok) 
   *ok = 1;
   for (int o = 0; o < c->m && *ok; ++o) {
     if ((rc = stage_down(c, &host, L.parity + o * L.shard_stride, 1, shard_len))) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    CEC_HIP_TRY(hipStreamSynchronize(c->stream));
     if (std::memcmp(par.data(), shards[c->k + o], shard_len) != 0) *ok = 0;
   }
   return CEC_OK;
@@ -2407,7 +2397,7 @@ int cec_encode_idx(cec_codec* c, const uint8_t* data_shard, int idx, uint8_t* co
   if (rc) return rc;
   for (int o = 0; o < c->m; ++o)
     if (!parity[o]) return set_err(CEC_EINVAL, "null parity shard");
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   const size_t stride = pad256(shard_len);
   rc = stage_ensure(c, 1 + (size_t)c->m, shard_len);
   if (rc) return rc;
@@ -2422,7 +2412,7 @@ int cec_encode_idx(cec_codec* c, const uint8_t* data_shard, int idx, uint8_t* co
   rc = check_launch();
   if (rc) return rc;
   if ((rc = stage_down(c, parity, d_par, c->m, shard_len))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  CEC_HIP_TRY(hipStreamSynchronize(c->stream));
   return CEC_OK;
 }
 
@@ -2441,7 +2431,7 @@ int cec_update(cec_codec* c, uint8_t* const* shards, const uint8_t* const* new_d
   for (int o = 0; o < c->m; ++o)
     if (!shards[c->k + o]) return set_err(CEC_EINVAL, "null parity shard");
   if (ch.empty()) return CEC_OK;
-  HIP_TRY(hipSetDevice(c->device));
+  CEC_HIP_TRY(hipSetDevice(c->device));
   const size_t stride = pad256(shard_len), nc = ch.size();
   rc = stage_ensure(c, 2 * nc + (size_t)c->m, shard_len);
   if (rc) return rc;
@@ -2461,7 +2451,7 @@ int cec_update(cec_codec* c, uint8_t* const* shards, const uint8_t* const* new_d
   rc = check_launch();
   if (rc) return rc;
   if ((rc = stage_down(c, shards + c->k, d_par, c->m, shard_len))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  CEC_HIP_TRY(hipStreamSynchronize(c->stream));
   return CEC_OK;
 }
 

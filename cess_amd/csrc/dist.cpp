@@ -33,20 +33,9 @@
 
 #include "../../include/cess_ec.h"
 #include "fftdec_plan.h"
-
-namespace cec {
-int set_error(int code, const std::string& msg);
-}
+#include "host_util.h"
 
 namespace {
-
-#define DI_TRY(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t _e = (expr);                                                                 \
-    if (_e != hipSuccess)                                                                   \
-      return cec::set_error(_e == hipErrorOutOfMemory ? CEC_ENOMEM : CEC_EHIP,              \
-                            std::string(#expr) + ": " + hipGetErrorString(_e));             \
-  } while (0)
 
 struct Rccl {
   bool ok = false;
@@ -232,10 +221,10 @@ namespace {
 // Grow a device buffer on `st` (the caller's stream, ordered after the previous call's `done`).
 int grow(uint8_t** buf, size_t* have, size_t need, hipStream_t st) {
   if (need <= *have) return CEC_OK;
-  if (*buf) DI_TRY(hipFreeAsync(*buf, st));
+  if (*buf) CEC_HIP_TRY(hipFreeAsync(*buf, st));
   *buf = nullptr;
   *have = 0;
-  DI_TRY(hipMallocAsync(reinterpret_cast<void**>(buf), need, st));
+  CEC_HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(buf), need, st));
   *have = need;
   return CEC_OK;
 }
@@ -454,7 +443,7 @@ int cec_dist_degraded_read(cec_dist* d, const uint64_t* lost_seg, const uint8_t*
 
   int prev = 0;
   (void)hipGetDevice(&prev);
-  DI_TRY(hipSetDevice(d->device));
+  CEC_HIP_TRY(hipSetDevice(d->device));
   struct Restore {
     int dev;
     ~Restore() { (void)hipSetDevice(dev); }
@@ -463,7 +452,7 @@ int cec_dist_degraded_read(cec_dist* d, const uint64_t* lost_seg, const uint8_t*
   if (d->broken) return cec::set_error(CEC_ENCCL, "dist degraded read: group aborted earlier");
   // after the previous call's tail (it may have run on another stream), and `done` recorded after
   // whatever this call enqueues, on every return path
-  if (d->used) DI_TRY(hipStreamWaitEvent(st, d->done, 0));
+  if (d->used) CEC_HIP_TRY(hipStreamWaitEvent(st, d->done, 0));
   struct Tail {
     cec_dist* d;
     hipStream_t st;
@@ -521,10 +510,10 @@ int cec_dist_degraded_read(cec_dist* d, const uint64_t* lost_seg, const uint8_t*
 
   // min over ranks of a success flag; every rank calls it at the same points
   auto agree = [&](int mine_ok, int* all_ok) -> int {
-    DI_TRY(hipMemcpyAsync(d->d_flag, &mine_ok, sizeof(int), hipMemcpyHostToDevice, st));
+    CEC_HIP_TRY(hipMemcpyAsync(d->d_flag, &mine_ok, sizeof(int), hipMemcpyHostToDevice, st));
     NC_TRY(r.all_reduce(d->d_flag, d->d_flag, 1, ncclInt32, ncclMin, d->comm, st));
-    DI_TRY(hipMemcpyAsync(all_ok, d->d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    DI_TRY(hipStreamSynchronize(st));
+    CEC_HIP_TRY(hipMemcpyAsync(all_ok, d->d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    CEC_HIP_TRY(hipStreamSynchronize(st));
     return CEC_OK;
   };
   // agree before any byte moves
@@ -704,7 +693,7 @@ int cec_dist_degraded_read(cec_dist* d, const uint64_t* lost_seg, const uint8_t*
   }
   // a failure after the last round's transfers leaves no peer waiting
   if (lrc) return cec::set_error(lrc, "dist degraded read: " + lwhy);
-  DI_TRY(hipStreamSynchronize(st));
+  CEC_HIP_TRY(hipStreamSynchronize(st));
   if (nrebuilt) *nrebuilt = rebuilt;
   return CEC_OK;
 }

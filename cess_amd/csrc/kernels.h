@@ -192,25 +192,22 @@ void launch_hashq_add(ShaChain* tab, uint32_t mask, uint64_t slot0, uint32_t n,
                       uint64_t len, uint8_t* hex, uint64_t hex_outer, uint64_t pre_blk,
                       uint8_t* pre_hex, uint64_t pre_hex_outer, hipStream_t st,
                       const uint32_t* h0 = nullptr, uint64_t blk0 = 0);
-// The same for n <= kHashqAddPtrs buffers at arbitrary device addresses (cec_hashq_add_ptrs):
-// chain i hashes the len bytes at src[i] (a HOST array, copied into the kernel arguments: a 2 KiB
-// block, under the 4 KiB limit) and writes its hex to hex + 64 * i (hex null: no output).
-constexpr uint32_t kHashqAddPtrs = 256;
-void launch_hashq_add_ptrs(ShaChain* tab, uint32_t mask, uint64_t slot0, uint32_t n,
-                           const uint8_t* const* src, uint64_t len, uint8_t* hex, hipStream_t st);
-// Chains over several buffers back to back (cec_hashq_add_concat_ptrs), n <= kHashqAddPtrs per
-// launch: chain i starts at src[i * stride] (a HOST array; stride = parts, so these are the
-// chains' first parts) with the whole chain's len, writes its hex to hex + 64 * i and, with
-// pre_hex, the hex of its first pre_blk blocks to pre_hex + 64 * i.
-void launch_hashq_add_concat(ShaChain* tab, uint32_t mask, uint64_t slot0, uint32_t n,
+// The same for n buffers at arbitrary device addresses (cec_hashq_add_ptrs: stride 1, no prefix)
+// and for chains over several buffers back to back (cec_hashq_add_concat_ptrs): chain i starts at
+// src[i * stride] (a HOST array; stride = parts, so these are the chains' first parts) with the
+// whole chain's len, writes its hex to hex + 64 * i (hex null: no output) and, with pre_hex, the
+// hex of its first pre_blk blocks to pre_hex + 64 * i. The addresses are copied into the kernel
+// arguments (a 2 KiB block, under the 4 KiB limit), one launch per 256 chains.
+// This launcher and the next stop at a launch that fails: the caller's launch check reports it.
+void launch_hashq_add_concat(ShaChain* tab, uint32_t mask, uint64_t slot0, uint64_t n,
                              const uint8_t* const* src, size_t stride, uint64_t len, uint8_t* hex,
                              uint64_t pre_blk, uint8_t* pre_hex, hipStream_t st);
-// Point n <= kHashqRebase chains in slots slot0.. at their next part: chain i's src becomes
-// addr[i * stride] - off (a HOST array, copied into the kernel arguments), off being the byte
-// position in the chain at which that part starts. The ticks then read the part as flat
-// src + blk * 64; the host keeps a launch from crossing into a part its chains are not based on.
-constexpr uint32_t kHashqRebase = 256;
-void launch_hashq_rebase(ShaChain* tab, uint32_t mask, uint64_t slot0, uint32_t n,
+// Point the n chains in slots slot0.. at their next part: chain i's src becomes
+// addr[i * stride] - off (a HOST array, copied into the kernel arguments, one launch per 256
+// chains), off being the byte position in the chain at which that part starts. The ticks then
+// read the part as flat src + blk * 64; the host keeps a launch from crossing into a part its
+// chains are not based on.
+void launch_hashq_rebase(ShaChain* tab, uint32_t mask, uint64_t slot0, uint64_t n,
                          const uint8_t* const* addr, size_t stride, uint64_t off, hipStream_t st);
 // Advance the n chains in slots head.. by at most max_blocks blocks each; tick_mode 0 lets `live`
 // (chains not yet complete among them) pick the kernel form, 1 or 2 = two waves with that many

@@ -46,21 +46,10 @@
 
 #include "../../include/cess_ec.h"
 #include "host_sha.h"
+#include "host_util.h"
 #include "kernels.h"
 
-namespace cec {
-int set_error(int code, const std::string& msg);
-}
-
 namespace {
-
-#define PL_TRY(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t _e = (expr);                                                                 \
-    if (_e != hipSuccess)                                                                   \
-      return cec::set_error(_e == hipErrorOutOfMemory ? CEC_ENOMEM : CEC_EHIP,              \
-                            std::string(#expr) + ": " + hipGetErrorString(_e));             \
-  } while (0)
 
 #define PL_RC(expr)          \
   do {                       \
@@ -182,14 +171,14 @@ struct cec_pipeline {
     }
     tail_batches = o.tail_batches;
     max_segments = o.max_segments;
-    PL_TRY(hipSetDevice(device));
+    CEC_HIP_TRY(hipSetDevice(device));
     // a slot is reused nd batches later; with GPU hashing its hashes are final `window` ticks
     // after its add, and two more slots keep the H2D of a reused slot from waiting on the tick
     // just enqueued. The window shrinks to what free HBM holds (one CESS slot is
     // ~1.5 GiB, so 35 slots are ~52 GiB, and several pipelines may share a GPU).
     const size_t slot_bytes = B * SB + B * (size_t)m * F + (gpu_hash() ? B * (k + m + 1) * 64 : 0);
     size_t free_b = 0, total_b = 0;
-    PL_TRY(hipMemGetInfo(&free_b, &total_b));
+    CEC_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     const size_t budget = (size_t)(0.85 * (double)free_b);
     if (gpu_hash()) {
       const size_t fit = slot_bytes ? budget / slot_bytes : 0;
@@ -207,21 +196,21 @@ struct cec_pipeline {
     if ((size_t)nd * slot_bytes > budget)
       return cec::set_error(CEC_ENOMEM, "pipeline: the device slots do not fit in free HBM");
     for (hipStream_t* s : {&s_h2d, &s_comp, &s_d2h})
-      PL_TRY(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+      CEC_HIP_TRY(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
     h_in.assign(depth, nullptr);
     h_par.assign(depth, nullptr);
     for (int i = 0; i < depth; ++i) {
-      PL_TRY(hipHostMalloc(&h_in[i], B * SB, hipHostMallocDefault));
-      PL_TRY(hipHostMalloc(&h_par[i], B * m * F, hipHostMallocDefault));
+      CEC_HIP_TRY(hipHostMalloc(&h_in[i], B * SB, hipHostMallocDefault));
+      CEC_HIP_TRY(hipHostMalloc(&h_par[i], B * m * F, hipHostMallocDefault));
     }
     d_data.assign(nd, nullptr);
     d_par.assign(nd, nullptr);
     for (auto* v : {&ev_h2d, &ev_enc, &ev_d2h, &ev_hex}) v->assign(nd, nullptr);
     for (int i = 0; i < nd; ++i) {
-      PL_TRY(hipMalloc(&d_data[i], B * SB));
-      PL_TRY(hipMalloc(&d_par[i], B * m * F));
+      CEC_HIP_TRY(hipMalloc(&d_data[i], B * SB));
+      CEC_HIP_TRY(hipMalloc(&d_par[i], B * m * F));
       for (auto* v : {&ev_h2d, &ev_enc, &ev_d2h, &ev_hex})
-        PL_TRY(hipEventCreateWithFlags(&(*v)[i], hipEventDisableTiming));
+        CEC_HIP_TRY(hipEventCreateWithFlags(&(*v)[i], hipEventDisableTiming));
     }
     if (gpu_hash()) {
       d_shex.assign(nd, nullptr);
@@ -229,10 +218,10 @@ struct cec_pipeline {
       h_shex.assign(nd, nullptr);
       h_fhex.assign(nd, nullptr);
       for (int i = 0; i < nd; ++i) {
-        PL_TRY(hipMalloc(&d_shex[i], B * 64));
-        PL_TRY(hipMalloc(&d_fhex[i], B * (k + m) * 64));
-        PL_TRY(hipHostMalloc(&h_shex[i], B * 64, hipHostMallocDefault));
-        PL_TRY(hipHostMalloc(&h_fhex[i], B * (k + m) * 64, hipHostMallocDefault));
+        CEC_HIP_TRY(hipMalloc(&d_shex[i], B * 64));
+        CEC_HIP_TRY(hipMalloc(&d_fhex[i], B * (k + m) * 64));
+        CEC_HIP_TRY(hipHostMalloc(&h_shex[i], B * 64, hipHostMallocDefault));
+        CEC_HIP_TRY(hipHostMalloc(&h_fhex[i], B * (k + m) * 64, hipHostMallocDefault));
       }
       // hybrid resume: needs fragment 0 on a block boundary. It halves the host's hashing on
       // hybrid batches (fragment 0 instead of the whole segment). With the host's 16 threads
@@ -250,8 +239,8 @@ struct cec_pipeline {
         ev_state.assign(nd, nullptr);
         state_pending.assign(nd, false);
         for (int i = 0; i < nd; ++i) {
-          PL_TRY(hipHostMalloc(&h_state[i], B * 32, hipHostMallocDefault));
-          PL_TRY(hipEventCreateWithFlags(&ev_state[i], hipEventDisableTiming));
+          CEC_HIP_TRY(hipHostMalloc(&h_state[i], B * 32, hipHostMallocDefault));
+          CEC_HIP_TRY(hipEventCreateWithFlags(&ev_state[i], hipEventDisableTiming));
         }
       }
       size_t chains = (size_t)(window + 1) * B * (k + m + 1), cap = 1024;
@@ -315,7 +304,7 @@ struct cec_pipeline {
     uint64_t t = 0;
     PL_RC(cec_hashq_add_resume(hq, d_data[b.ds], b.nseg, 1, SB, SB, SB, F, h_state[b.ds],
                                d_shex[b.ds], 1, &t));
-    PL_TRY(hipEventRecord(ev_state[b.ds], s_comp));  // h_state[ds] reusable once read
+    CEC_HIP_TRY(hipEventRecord(ev_state[b.ds], s_comp));  // h_state[ds] reusable once read
     state_pending[b.ds] = true;
     b.ticket = t;
     b.resume_added = true;
@@ -334,11 +323,11 @@ struct cec_pipeline {
     PL_RC(add_resume(b, true));
     while (!hashed(b)) PL_RC(cec_hashq_tick(hq, tick_blocks));
     if (b.gpu_seg || b.seg_resume)
-      PL_TRY(hipMemcpyAsync(h_shex[b.ds], d_shex[b.ds], b.nseg * 64, hipMemcpyDeviceToHost,
-                            s_comp));
-    PL_TRY(hipMemcpyAsync(h_fhex[b.ds], d_fhex[b.ds], b.nseg * (k + m) * 64,
-                          hipMemcpyDeviceToHost, s_comp));
-    PL_TRY(hipEventRecord(ev_hex[b.ds], s_comp));
+      CEC_HIP_TRY(hipMemcpyAsync(h_shex[b.ds], d_shex[b.ds], b.nseg * 64, hipMemcpyDeviceToHost,
+                                 s_comp));
+    CEC_HIP_TRY(hipMemcpyAsync(h_fhex[b.ds], d_fhex[b.ds], b.nseg * (k + m) * 64,
+                               hipMemcpyDeviceToHost, s_comp));
+    CEC_HIP_TRY(hipEventRecord(ev_hex[b.ds], s_comp));
     b.hex_copied = true;
     return CEC_OK;
   }
@@ -469,12 +458,12 @@ int cec_pipeline_run_files(cec_pipeline* p, const cec_source* srcs, size_t nsrc,
     if (!srcs[f].read) return cec::set_error(CEC_EINVAL, "null read callback");
   if (on_record && p->mode == CEC_PIPE_HASH_NONE)
     return cec::set_error(CEC_EINVAL, "on_record needs hashing (hash != 0)");
-  PL_TRY(hipSetDevice(p->device));
+  CEC_HIP_TRY(hipSetDevice(p->device));
   // start clean after an aborted run: no queued copies, no live chains of the old batches, no
   // host jobs reading the ring
   if (p->hq) PL_RC(cec_hashq_finish(p->hq));
   for (hipStream_t s : {p->s_h2d, p->s_comp, p->s_d2h})
-    if (s) PL_TRY(hipStreamSynchronize(s));
+    if (s) CEC_HIP_TRY(hipStreamSynchronize(s));
   p->wait_host_jobs();
   const double t0 = now_s();
   const hsha::PoolStats ps0 = hsha::stats();
@@ -535,7 +524,8 @@ int cec_pipeline_run_files(cec_pipeline* p, const cec_source* srcs, size_t nsrc,
   // on_fragments of batch b (its parity D2H complete); shards straight from the pinned slots
   auto deliver_frags = [&](Batch& b) -> int {
     const double w = now_s();
-    PL_TRY(hipEventSynchronize(p->ev_d2h[b.ds]));  // (a later reuse of the slot only waits more)
+    // (a later reuse of the slot only waits more)
+    CEC_HIP_TRY(hipEventSynchronize(p->ev_d2h[b.ds]));
     t_wait += now_s() - w;
     w_d2h += now_s() - w;
     p->submit_host_parity(b);
@@ -595,7 +585,7 @@ int cec_pipeline_run_files(cec_pipeline* p, const cec_source* srcs, size_t nsrc,
       const double w = now_s();
       if (b.gpu) {
         if (!b.hex_copied) PL_RC(p->copy_hex(b));  // its slot's previous batch is popped
-        PL_TRY(hipEventSynchronize(p->ev_hex[b.ds]));
+        CEC_HIP_TRY(hipEventSynchronize(p->ev_hex[b.ds]));
       }
       p->host_wait(b);
       t_wait += now_s() - w;
@@ -672,8 +662,8 @@ int cec_pipeline_run_files(cec_pipeline* p, const cec_source* srcs, size_t nsrc,
     if (i >= (uint64_t)p->nd) {
       // device slot ds: its previous batch's parity read out and (hashing) its hex copied out
       if (p->gpu_hash()) PL_RC(hex_through(i - p->nd));
-      PL_TRY(hipStreamWaitEvent(p->s_h2d, p->ev_d2h[ds], 0));
-      if (p->gpu_hash()) PL_TRY(hipStreamWaitEvent(p->s_h2d, p->ev_hex[ds], 0));
+      CEC_HIP_TRY(hipStreamWaitEvent(p->s_h2d, p->ev_d2h[ds], 0));
+      if (p->gpu_hash()) CEC_HIP_TRY(hipStreamWaitEvent(p->s_h2d, p->ev_hex[ds], 0));
     }
     inflight.emplace_back();
     Batch& b = inflight.back();
@@ -693,21 +683,21 @@ int cec_pipeline_run_files(cec_pipeline* p, const cec_source* srcs, size_t nsrc,
     fs.batches_open++;
     segs_total += nseg;
     if (p->host_hash()) p->submit_host_data(b);
-    PL_TRY(hipMemcpyAsync(p->d_data[ds], dst, nseg * p->SB, hipMemcpyHostToDevice, p->s_h2d));
-    PL_TRY(hipEventRecord(p->ev_h2d[ds], p->s_h2d));
-    PL_TRY(hipStreamWaitEvent(p->s_comp, p->ev_h2d[ds], 0));
+    CEC_HIP_TRY(hipMemcpyAsync(p->d_data[ds], dst, nseg * p->SB, hipMemcpyHostToDevice, p->s_h2d));
+    CEC_HIP_TRY(hipEventRecord(p->ev_h2d[ds], p->s_h2d));
+    CEC_HIP_TRY(hipStreamWaitEvent(p->s_comp, p->ev_h2d[ds], 0));
     PL_RC(cec_encode_batch(p->codec, p->d_data[ds], p->d_par[ds], nseg, p->F, p->s_comp));
-    PL_TRY(hipEventRecord(p->ev_enc[ds], p->s_comp));
-    PL_TRY(hipStreamWaitEvent(p->s_d2h, p->ev_enc[ds], 0));
-    PL_TRY(hipMemcpyAsync(p->h_par[hs], p->d_par[ds], nseg * p->m * p->F, hipMemcpyDeviceToHost,
-                          p->s_d2h));
-    PL_TRY(hipEventRecord(p->ev_d2h[ds], p->s_d2h));
+    CEC_HIP_TRY(hipEventRecord(p->ev_enc[ds], p->s_comp));
+    CEC_HIP_TRY(hipStreamWaitEvent(p->s_d2h, p->ev_enc[ds], 0));
+    CEC_HIP_TRY(hipMemcpyAsync(p->h_par[hs], p->d_par[ds], nseg * p->m * p->F,
+                               hipMemcpyDeviceToHost, p->s_d2h));
+    CEC_HIP_TRY(hipEventRecord(p->ev_d2h[ds], p->s_d2h));
     if (b.gpu) {
       PL_RC(p->add_gpu_hashes(b));  // on s_comp, after the encode
     } else if (p->gpu_hash()) {
       // nothing of this batch on the queue: its slot is free for reuse after the encode, and
       // the queue still ticks for the chains of earlier batches
-      PL_TRY(hipEventRecord(p->ev_hex[ds], p->s_comp));
+      CEC_HIP_TRY(hipEventRecord(p->ev_hex[ds], p->s_comp));
       PL_RC(cec_hashq_tick(p->hq, p->tick_blocks));
     }
     // resumed segment chains of the batches whose fragment-0 host jobs are done
@@ -745,7 +735,7 @@ int cec_pipeline_run_files(cec_pipeline* p, const cec_source* srcs, size_t nsrc,
   if (p->hq) PL_RC(cec_hashq_finish(p->hq));
   if (i) PL_RC(records_through(i - 1));
   for (hipStream_t s : {p->s_h2d, p->s_comp, p->s_d2h})
-    if (s) PL_TRY(hipStreamSynchronize(s));
+    if (s) CEC_HIP_TRY(hipStreamSynchronize(s));
   p->wait_host_jobs();
   PL_RC(files_done());
   if (getenv("CEC_PIPELINE_TRACE")) {

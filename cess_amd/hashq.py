@@ -28,6 +28,29 @@ def sha256_blocks(length: int) -> int:
     return (length >> 6) + (2 if (length & 63) >= 56 else 1)
 
 
+def _at(d, offset: int = 0):
+    """The device address of `d` plus `offset` bytes; None stays None (a null pointer in C)."""
+    return None if d is None else _dev_ptr(d) + offset
+
+
+def _rows(rows, width: Optional[int] = None):
+    """Rows of 1-D tensors as (rows as lists, their tensors in one list, the tensors' one size; 0
+    without tensors). Rows that are not `width` long (None: as long as the first) or tensors of
+    different sizes raise ErrShardSize, a None entry ErrInvalidInput."""
+    rows = [list(row) for row in rows]
+    if width is None and rows:
+        width = len(rows[0])
+    if any(len(row) != width for row in rows):
+        raise ErrShardSize(ErrShardSize.__doc__)
+    flat = [t for row in rows for t in row]
+    if any(t is None for t in flat):
+        raise ErrInvalidInput(ErrInvalidInput.__doc__)
+    sizes = {t.numel() for t in flat}
+    if len(sizes) > 1:
+        raise ErrShardSize(ErrShardSize.__doc__)
+    return rows, flat, sizes.pop() if sizes else 0
+
+
 class HashQueue:
     """GPU hash queue bound to one device and one stream (all its work is ordered there)."""
 
@@ -66,8 +89,7 @@ class HashQueue:
         at d_prefix_hex + prefix_hex_offset + ((i // per) * prefix_hex_outer + i % per) * 64
         (cec_hashq_add_prefix). Returns the add's ticket."""
         t = c_uint64()
-        hexp = None if d_hex is None else _dev_ptr(d_hex) + hex_offset
-        prep = None if d_prefix_hex is None else _dev_ptr(d_prefix_hex) + prefix_hex_offset
+        hexp, prep = _at(d_hex, hex_offset), _at(d_prefix_hex, prefix_hex_offset)
         check(_lib.load().cec_hashq_add_prefix(self._h, _dev_ptr(d_base), n, per, outer_stride,
                                                inner_stride, length, hexp, hex_outer,
                                                prefix_len if prep else 0, prep,
@@ -85,11 +107,9 @@ class HashQueue:
         them) and hashes bytes start_len .. length of its buffer. The states are read by the
         add's kernel on the queue's stream. Returns the add's ticket (0 for n == 0)."""
         t = c_uint64()
-        hexp = None if d_hex is None else _dev_ptr(d_hex) + hex_offset
-        states = None if d_states is None else _dev_ptr(d_states)
         check(_lib.load().cec_hashq_add_resume(self._h, _dev_ptr(d_base), n, per, outer_stride,
-                                               inner_stride, length, start_len, states, hexp,
-                                               hex_outer, byref(t)),
+                                               inner_stride, length, start_len, _at(d_states),
+                                               _at(d_hex, hex_offset), hex_outer, byref(t)),
               "HashQueue.add_resume")
         return t.value
 
@@ -106,10 +126,10 @@ class HashQueue:
         if len(sizes) > 1:
             raise ErrShardSize(ErrShardSize.__doc__)
         length = sizes.pop() if sizes else 0
-        ptrs = (c_void_p * max(1, n))(*[None if t is None else _dev_ptr(t) for t in tensors])
+        ptrs = (c_void_p * max(1, n))(*[_at(t) for t in tensors])
         t = c_uint64()
-        hexp = None if d_hex is None else _dev_ptr(d_hex) + hex_offset
-        check(_lib.load().cec_hashq_add_ptrs(self._h, ptrs, n, length, hexp, byref(t)),
+        check(_lib.load().cec_hashq_add_ptrs(self._h, ptrs, n, length, _at(d_hex, hex_offset),
+                                             byref(t)),
               "HashQueue.add_ptrs")
         return t.value
 
@@ -125,26 +145,16 @@ class HashQueue:
         ErrShardNoData, before any C call; what the library refuses (a size that is no multiple
         of 64, a `length` that does not end in the last tensor) raises ErrInvalidInput with the
         ring unchanged. Returns the add's ticket (0 for an empty sequence, without a C call)."""
-        chains = [list(row) for row in chains]
+        chains, flat, part_len = _rows(chains)
         n = len(chains)
         if n == 0:
             return 0
         parts = len(chains[0])
-        if any(len(row) != parts for row in chains):
-            raise ErrShardSize(ErrShardSize.__doc__)
-        flat = [t for row in chains for t in row]
-        if any(t is None for t in flat):
-            raise ErrInvalidInput(ErrInvalidInput.__doc__)
-        sizes = {t.numel() for t in flat}
-        if len(sizes) > 1:
-            raise ErrShardSize(ErrShardSize.__doc__)
-        part_len = sizes.pop() if sizes else 0
         if part_len == 0:
             raise ErrShardNoData(ErrShardNoData.__doc__)
         ptrs = (c_void_p * len(flat))(*[_dev_ptr(t) for t in flat])
         t = c_uint64()
-        hexp = None if d_hex is None else _dev_ptr(d_hex) + hex_offset
-        prep = None if d_prefix_hex is None else _dev_ptr(d_prefix_hex) + prefix_hex_offset
+        hexp, prep = _at(d_hex, hex_offset), _at(d_prefix_hex, prefix_hex_offset)
         try:
             check(_lib.load().cec_hashq_add_concat_ptrs(self._h, ptrs, n, parts, part_len,
                                                         0 if length is None else length, hexp,
@@ -211,19 +221,13 @@ class HashQueue:
         an add_ptrs hashes fragments 1..k+m-1. Nothing is copied. Returns the ticket of the last
         segment chain: the segment chains are the longest and complete in the same tick (0 for
         no segments)."""
-        segments = [list(seg) for seg in segments]
         n_sh = k + m
-        if any(len(seg) != n_sh for seg in segments):
-            raise ErrShardSize(ErrShardSize.__doc__)
+        segments, _, size = _rows(segments, n_sh)
         if not segments:
             return 0
-        flat = [t for seg in segments for t in seg]
-        if any(t is None for t in flat):
-            raise ErrInvalidInput(ErrInvalidInput.__doc__)
-        sizes = {t.numel() for t in flat}
-        if len(sizes) > 1 or next(iter(sizes)) % 64:
+        if size % 64:
             raise ErrShardSize(ErrShardSize.__doc__)
-        if 0 in sizes:
+        if size == 0:
             raise ErrShardNoData(ErrShardNoData.__doc__)
         # the C calls lay their hex out 64 bytes apart, a segment's fragment slots lie in its own
         # row of d_frag_hex: so one concat add and one pointer add per segment, a few small

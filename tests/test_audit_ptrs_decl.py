@@ -120,7 +120,7 @@ def test_new_kernels_use_no_scratch():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import sha_slots
     res = sha_slots.kernel_resources(_lib.LIB_PATH)
-    for pat, count in (("k_chunk_gather_tab", 2), ("k_chunk_addrs", 1), ("k_hashq_add_ptrs", 1)):
+    for pat, count in (("k_chunk_gather_tab", 2), ("k_chunk_addrs", 1), ("k_hashq_add_concat", 1)):
         ks = {n: r for n, r in res.items() if pat in n}
         assert len(ks) == count, (pat, sorted(ks))
         for n, r in ks.items():

@@ -148,6 +148,24 @@ def test_ring_wrap(torch, cess):
     q.close()
 
 
+def test_two_launches_across_the_wrap_with_and_without_output(torch, cess):
+    """257 chains are two add launches, the second of one chain: with no output it must not make
+    an address of the null hex, and its slots follow the first launch's over the wrap point."""
+    _, bufs, want = case(torch, 300, 56)
+    q = mkq(cess, 0, capacity=512)
+    # slots 0..299, 300..556 (wraps, no output), 557..813, 814..1070 (wraps)
+    for lo, n, out in ((0, 300, True), (0, 257, False), (43, 257, True), (0, 257, True)):
+        d_hex = torch.zeros((n, 64), dtype=torch.uint8, device="cuda") if out else None
+        t = q.add_ptrs(bufs[lo:lo + n], d_hex)
+        assert q.live_chains == n
+        q.finish()
+        torch.cuda.synchronize()
+        assert q.done(t) and q.live_chains == 0
+        if out:
+            assert np.array_equal(d_hex.cpu().numpy(), want[lo:lo + n]), (lo, n)
+    q.close()
+
+
 def test_queue_full_adds_nothing(torch, cess):
     _, bufs, want = case(torch, 300, 4113)
     q = mkq(cess, 0, capacity=64)

@@ -127,5 +127,6 @@ def test_new_kernels_use_no_scratch_and_the_ticks_are_as_many():
         for n, r in ks.items():
             assert int(r["private_segment_fixed_size"]) == 0, (n, r["private_segment_fixed_size"])
             assert int(r["vgpr_spill_count"]) == 0 and int(r["sgpr_spill_count"]) == 0, n
-    assert len([n for n in res if "k_hashq_add_ptrs" in n]) == 1
+    # the pointer add is the concat add with one part: two add kernels, strided and by address
+    assert len([n for n in res if "k_hashq_add" in n]) == 2
     assert len([n for n in res if "k_sha256_tick" in n]) == 4

@@ -4,7 +4,8 @@ compares the queue's bookkeeping with the model's after every operation, so what
 is that the committed script is worth playing: it wraps the ring, mixes every kind of add, fills
 the ring and puts resumed chains across the wrap point. Pure Python, no GPU and no library.
 
-The model mirrors cess_amd/csrc/hashq.cpp: adds in slot order as (slot0, n, blocks, done), a tick
+The model mirrors cess_amd/csrc/hashq_ring.h (tests/test_hashq_ring.py plays this script on the
+ring itself and compares): adds in slot order as (slot0, n, blocks, done), a tick
 of T blocks advances every add by min(T, blocks left), completed adds retire from the front only,
 head is the oldest listed add's slot0 and an add of n chains is refused exactly when
 tail + n - head > capacity."""
