@@ -98,3 +98,34 @@ def audit_chunks_device(enc: Encoder, frags: Sequence, indices: Sequence[int], d
         idx.size, None if d_chunks is None else _dev_ptr(d_chunks),
         None if d_hex is None else _dev_ptr(d_hex), enc._device_stream(stream)),
         "audit_chunks_device")
+
+
+def scrub_device(frags: Sequence, recorded, queue=None, d_ok=None):
+    """A miner's scrub: does each stored fragment still hash to what the chain recorded for it
+    (`FragmentInfo.hash`)? `frags` is a sequence of 1-D uint8 device tensors of one length, each
+    wherever it lies; `recorded` their hashes, a list of 64-byte `bytes` or a device / pinned
+    uint8 tensor [n][64]. Returns a uint8 device tensor (d_ok, or a new one): flag f is 1 where
+    SHA-256(frags[f]) equals recorded[f], else 0, written on the GPU by the hash queue's ticks
+    (HashQueue.add_check_ptrs). The chains are added and ticked to completion on `queue`'s stream
+    and nothing is waited for: the flags are final when that stream gets there. queue None: a
+    queue of the call's size on torch's current stream, owned and closed by the call (creating a
+    queue waits once for its table's allocation; a service that scrubs again and again keeps
+    one)."""
+    import torch
+    from .hashq import HashQueue
+    frags = list(frags)
+    if queue is not None:
+        _, d_ok = queue.add_check_ptrs(frags, recorded, d_ok)
+        queue.finish()
+        return d_ok
+    if not frags:
+        return torch.empty(0, dtype=torch.uint8, device="cuda") if d_ok is None else d_ok
+    if any(t is None for t in frags):
+        raise ErrInvalidInput(ErrInvalidInput.__doc__)
+    dev = frags[0].device
+    cap = 1 << max(0, len(frags) - 1).bit_length()
+    with HashQueue(capacity=cap, device=dev.index or 0,
+                   stream=torch.cuda.current_stream(dev)) as q:
+        _, d_ok = q.add_check_ptrs(frags, recorded, d_ok)
+        q.finish()
+    return d_ok

@@ -64,34 +64,85 @@ int add_chains(cec_hashq* q, size_t n, uint64_t blocks, uint64_t* ticket, L laun
   return CEC_OK;
 }
 
-// Strided chains (cec_hashq_add_prefix, cec_hashq_add_resume): pre_blk with d_prefix_hex, blk0
-// with d_states.
+// The recorded hashes a checking add compares with and the flags it writes (both null: no check).
+struct Check {
+  const uint8_t* expect = nullptr;
+  size_t expect_outer = 0;
+  uint8_t* ok = nullptr;
+  size_t ok_outer = 0;
+};
+
+// What the checking adds ask of their own arguments, before anything else is looked at.
+int check_args(const cec_hashq* q, size_t n, const uint8_t* d_expect, const uint8_t* d_ok) {
+  if (!q) return cec::set_error(CEC_EINVAL, "null");
+  if (n && (!d_expect || !d_ok))
+    return cec::set_error(CEC_EINVAL, "a checking add needs d_expect and d_ok");
+  if ((uintptr_t)d_expect & 3) return cec::set_error(CEC_EINVAL, "d_expect must be 4-byte aligned");
+  return CEC_OK;
+}
+
+// Strided chains (cec_hashq_add_prefix, cec_hashq_add_resume, cec_hashq_add_check): pre_blk with
+// d_prefix_hex, blk0 with d_states, the check with c.ok.
 int add_strided(cec_hashq* q, const uint8_t* d_base, size_t n, size_t per, size_t outer_stride,
                 size_t inner_stride, size_t len, uint8_t* d_hex, size_t hex_outer, uint64_t pre_blk,
                 uint8_t* d_prefix_hex, size_t prefix_hex_outer, const uint32_t* d_states,
-                uint64_t blk0, uint64_t* ticket) {
+                uint64_t blk0, const Check& c, uint64_t* ticket) {
   return add_chains(q, n, cec::sha256_blocks(len) - blk0, ticket, [&](uint64_t slot0) {
     cec::launch_hashq_add(q->tab, q->mask(), slot0, (uint32_t)n, d_base, (uint32_t)per,
                           outer_stride, inner_stride, len, d_hex, hex_outer, pre_blk, d_prefix_hex,
-                          prefix_hex_outer, q->stream, d_states, blk0);
+                          prefix_hex_outer, c.expect, c.expect_outer, c.ok, c.ok_outer, q->stream,
+                          d_states, blk0);
   });
 }
 
-// Chains by address table (cec_hashq_add_ptrs: parts = 1, no prefix; cec_hashq_add_concat_ptrs):
+// Chains by address table (cec_hashq_add_ptrs: parts = 1, no prefix; cec_hashq_add_concat_ptrs;
+// cec_hashq_add_check_concat_ptrs: either, checked against c.expect + 64 * i into c.ok + i):
 // the first parts' addresses go in the kernel arguments, so the array is the caller's again on
 // return and nothing waits for the ticks queued before. One part: nothing to move to, nothing
 // kept.
 int add_table(cec_hashq* q, const uint8_t* const* d_parts, size_t n, size_t parts,
               size_t part_blocks, size_t len, uint8_t* d_hex, uint8_t* d_prefix_hex,
-              uint64_t* ticket) {
+              const Check& c, uint64_t* ticket) {
   const bool concat = parts > 1;
   return add_chains(
       q, n, cec::sha256_blocks(len), ticket,
       [&](uint64_t slot0) {
         cec::launch_hashq_add_concat(q->tab, q->mask(), slot0, n, d_parts, parts, len, d_hex,
-                                     part_blocks, d_prefix_hex, q->stream);
+                                     part_blocks, d_prefix_hex, c.expect, c.ok, q->stream);
       },
       concat ? parts : 0, concat ? part_blocks : 0, concat ? d_parts : nullptr);
+}
+
+// The argument checks and the add of cec_hashq_add_ptrs and of cec_hashq_add_concat_ptrs, shared
+// with their checking form.
+int add_ptrs(cec_hashq* q, const uint8_t* const* d_bufs, size_t n, size_t len, uint8_t* d_hex,
+             const Check& c, uint64_t* ticket) {
+  if (!q || (n && !d_bufs)) return cec::set_error(CEC_EINVAL, "null");
+  if (n > 0xFFFFFFFFull) return cec::set_error(CEC_EINVAL, "n too large");
+  for (size_t i = 0; i < n; ++i)
+    if (!d_bufs[i]) return cec::set_error(CEC_EINVAL, "null buffer");
+  return add_table(q, d_bufs, n, 1, 0, len, d_hex, nullptr, c, ticket);
+}
+
+int add_concat_ptrs(cec_hashq* q, const uint8_t* const* d_parts, size_t n, size_t parts,
+                    size_t part_len, size_t len, uint8_t* d_hex, uint8_t* d_prefix_hex,
+                    const Check& c, uint64_t* ticket) {
+  if (!q || (n && !d_parts)) return cec::set_error(CEC_EINVAL, "null");
+  if (parts == 0) return cec::set_error(CEC_EINVAL, "parts == 0");
+  if (part_len == 0 || (part_len & 63))
+    return cec::set_error(CEC_EINVAL, "part_len must be a nonzero multiple of 64");
+  if (parts > ~(size_t)0 / part_len) return cec::set_error(CEC_EINVAL, "parts * part_len overflows");
+  if (len == 0) len = parts * part_len;
+  if (len <= (parts - 1) * part_len || len > parts * part_len)
+    return cec::set_error(CEC_EINVAL, "len must end inside the last part");
+  if (d_prefix_hex && len < part_len)
+    return cec::set_error(CEC_EINVAL, "the prefix digest needs a whole first part");
+  if (n > 0xFFFFFFFFull) return cec::set_error(CEC_EINVAL, "n too large");
+  if (n && parts > ~(size_t)0 / sizeof(void*) / n)
+    return cec::set_error(CEC_EINVAL, "n * parts overflows");
+  for (size_t i = 0; i < n * parts; ++i)
+    if (!d_parts[i]) return cec::set_error(CEC_EINVAL, "null buffer");
+  return add_table(q, d_parts, n, parts, part_len >> 6, len, d_hex, d_prefix_hex, c, ticket);
 }
 
 }  // namespace
@@ -144,7 +195,7 @@ int cec_hashq_add_prefix(cec_hashq* q, const uint8_t* d_base, size_t n, size_t p
     return cec::set_error(CEC_EINVAL, "prefix_len must be a nonzero multiple of 64 <= len");
   return add_strided(q, d_base, n, per, outer_stride, inner_stride, len, d_hex, hex_outer,
                      d_prefix_hex ? prefix_len >> 6 : 0, d_prefix_hex, prefix_hex_outer, nullptr, 0,
-                     ticket);
+                     Check{}, ticket);
 }
 
 int cec_hashq_add_resume(cec_hashq* q, const uint8_t* d_base, size_t n, size_t per,
@@ -157,7 +208,7 @@ int cec_hashq_add_resume(cec_hashq* q, const uint8_t* d_base, size_t n, size_t p
   if ((start_len & 63) || start_len > (len & ~(size_t)63))
     return cec::set_error(CEC_EINVAL, "start_len must be a multiple of 64 within len's full blocks");
   return add_strided(q, d_base, n, per, outer_stride, inner_stride, len, d_hex, hex_outer, 0,
-                     nullptr, 0, d_states, start_len >> 6, ticket);
+                     nullptr, 0, d_states, start_len >> 6, Check{}, ticket);
 }
 
 int cec_hashq_add(cec_hashq* q, const uint8_t* d_base, size_t n, size_t per, size_t outer_stride,
@@ -169,32 +220,38 @@ int cec_hashq_add(cec_hashq* q, const uint8_t* d_base, size_t n, size_t per, siz
 
 int cec_hashq_add_ptrs(cec_hashq* q, const uint8_t* const* d_bufs, size_t n, size_t len,
                        uint8_t* d_hex, uint64_t* ticket) {
-  if (!q || (n && !d_bufs)) return cec::set_error(CEC_EINVAL, "null");
-  if (n > 0xFFFFFFFFull) return cec::set_error(CEC_EINVAL, "n too large");
-  for (size_t i = 0; i < n; ++i)
-    if (!d_bufs[i]) return cec::set_error(CEC_EINVAL, "null buffer");
-  return add_table(q, d_bufs, n, 1, 0, len, d_hex, nullptr, ticket);
+  return add_ptrs(q, d_bufs, n, len, d_hex, Check{}, ticket);
 }
 
 int cec_hashq_add_concat_ptrs(cec_hashq* q, const uint8_t* const* d_parts, size_t n, size_t parts,
                               size_t part_len, size_t len, uint8_t* d_hex, uint8_t* d_prefix_hex,
                               uint64_t* ticket) {
-  if (!q || (n && !d_parts)) return cec::set_error(CEC_EINVAL, "null");
-  if (parts == 0) return cec::set_error(CEC_EINVAL, "parts == 0");
-  if (part_len == 0 || (part_len & 63))
-    return cec::set_error(CEC_EINVAL, "part_len must be a nonzero multiple of 64");
-  if (parts > ~(size_t)0 / part_len) return cec::set_error(CEC_EINVAL, "parts * part_len overflows");
-  if (len == 0) len = parts * part_len;
-  if (len <= (parts - 1) * part_len || len > parts * part_len)
-    return cec::set_error(CEC_EINVAL, "len must end inside the last part");
-  if (d_prefix_hex && len < part_len)
-    return cec::set_error(CEC_EINVAL, "the prefix digest needs a whole first part");
+  return add_concat_ptrs(q, d_parts, n, parts, part_len, len, d_hex, d_prefix_hex, Check{},
+                         ticket);
+}
+
+int cec_hashq_add_check(cec_hashq* q, const uint8_t* d_base, size_t n, size_t per,
+                        size_t outer_stride, size_t inner_stride, size_t len,
+                        const uint8_t* d_expect, size_t expect_outer, uint8_t* d_ok, size_t ok_outer,
+                        uint8_t* d_hex, size_t hex_outer, uint64_t* ticket) {
+  int rc = check_args(q, n, d_expect, d_ok);
+  if (rc) return rc;
+  if ((n && !d_base) || per == 0) return cec::set_error(CEC_EINVAL, "null or per == 0");
   if (n > 0xFFFFFFFFull) return cec::set_error(CEC_EINVAL, "n too large");
-  if (n && parts > ~(size_t)0 / sizeof(void*) / n)
-    return cec::set_error(CEC_EINVAL, "n * parts overflows");
-  for (size_t i = 0; i < n * parts; ++i)
-    if (!d_parts[i]) return cec::set_error(CEC_EINVAL, "null buffer");
-  return add_table(q, d_parts, n, parts, part_len >> 6, len, d_hex, d_prefix_hex, ticket);
+  return add_strided(q, d_base, n, per, outer_stride, inner_stride, len, d_hex, hex_outer, 0,
+                     nullptr, 0, nullptr, 0, Check{d_expect, expect_outer, d_ok, ok_outer}, ticket);
+}
+
+int cec_hashq_add_check_concat_ptrs(cec_hashq* q, const uint8_t* const* d_parts, size_t n,
+                                    size_t parts, size_t part_len, size_t len,
+                                    const uint8_t* d_expect, uint8_t* d_ok, uint8_t* d_hex,
+                                    uint8_t* d_prefix_hex, uint64_t* ticket) {
+  int rc = check_args(q, n, d_expect, d_ok);
+  if (rc) return rc;
+  const Check c{d_expect, 0, d_ok, 0};
+  // one buffer per chain is cec_hashq_add_ptrs: any len, part_len not used, no prefix to give
+  if (parts == 1 && !d_prefix_hex) return add_ptrs(q, d_parts, n, len, d_hex, c, ticket);
+  return add_concat_ptrs(q, d_parts, n, parts, part_len, len, d_hex, d_prefix_hex, c, ticket);
 }
 
 int cec_hashq_tick(cec_hashq* q, uint32_t max_blocks) {

@@ -169,6 +169,10 @@ void launch_sha256_hex(int sha_mode, const uint8_t* const* ptrs, const Layout* L
 // by the launch that completes it. Prefix digest: when `pre_blk` > 0 the chain also writes the
 // SHA-256 hex of its first pre_blk * 64 bytes to `pre_hex`, from a copy of `h` taken right after
 // block pre_blk - 1 and one padding block (a segment's chain gives its first fragment's hash).
+// Check: when `ok` is set the completing launch also compares the 64 hex characters of the digest
+// with the 64 bytes at `expect` (4-byte aligned, read as words) and stores *ok = 1 (equal) or 0;
+// a launch that leaves the chain unfinished writes nothing there. The prefix digest is an output
+// only: the record has room for one (expect, ok) pair.
 struct ShaChain {
   const uint8_t* src;
   uint64_t len;
@@ -178,7 +182,8 @@ struct ShaChain {
   uint8_t* pre_hex;
   uint64_t pre_blk;
   uint32_t pre_h[8];  // state after pre_blk blocks, parked by the one-wave tick until its loop ends
-  uint64_t pad_[2];
+  const uint8_t* expect;  // the recorded hash to compare with, 64 lowercase hex chars (null with ok)
+  uint8_t* ok;            // where the comparison's flag goes (null: no check)
 };
 static_assert(sizeof(ShaChain) == 128, "ShaChain is one 128-byte record");
 
@@ -186,22 +191,27 @@ __host__ __device__ inline uint64_t sha256_blocks(uint64_t len) { return (len >>
 
 // Initialise n chains in slots slot0.. of the ring `tab` (capacity mask + 1, a power of two).
 // pre_blk > 0: chain i also writes the hex of its first pre_blk blocks to
-// pre_hex + ((i / per) * pre_hex_outer + i % per) * 64.
+// pre_hex + ((i / per) * pre_hex_outer + i % per) * 64. ok set: chain i is checked against
+// expect + ((i / per) * expect_outer + i % per) * 64, its flag goes to
+// ok + (i / per) * ok_outer + i % per.
 void launch_hashq_add(ShaChain* tab, uint32_t mask, uint64_t slot0, uint32_t n,
                       const uint8_t* base, uint32_t per, uint64_t outer, uint64_t inner,
                       uint64_t len, uint8_t* hex, uint64_t hex_outer, uint64_t pre_blk,
-                      uint8_t* pre_hex, uint64_t pre_hex_outer, hipStream_t st,
+                      uint8_t* pre_hex, uint64_t pre_hex_outer, const uint8_t* expect,
+                      uint64_t expect_outer, uint8_t* ok, uint64_t ok_outer, hipStream_t st,
                       const uint32_t* h0 = nullptr, uint64_t blk0 = 0);
 // The same for n buffers at arbitrary device addresses (cec_hashq_add_ptrs: stride 1, no prefix)
 // and for chains over several buffers back to back (cec_hashq_add_concat_ptrs): chain i starts at
 // src[i * stride] (a HOST array; stride = parts, so these are the chains' first parts) with the
 // whole chain's len, writes its hex to hex + 64 * i (hex null: no output) and, with pre_hex, the
-// hex of its first pre_blk blocks to pre_hex + 64 * i. The addresses are copied into the kernel
+// hex of its first pre_blk blocks to pre_hex + 64 * i; with ok, it is checked against
+// expect + 64 * i and flagged in ok + i. The addresses are copied into the kernel
 // arguments (a 2 KiB block, under the 4 KiB limit), one launch per 256 chains.
 // This launcher and the next stop at a launch that fails: the caller's launch check reports it.
 void launch_hashq_add_concat(ShaChain* tab, uint32_t mask, uint64_t slot0, uint64_t n,
                              const uint8_t* const* src, size_t stride, uint64_t len, uint8_t* hex,
-                             uint64_t pre_blk, uint8_t* pre_hex, hipStream_t st);
+                             uint64_t pre_blk, uint8_t* pre_hex, const uint8_t* expect,
+                             uint8_t* ok, hipStream_t st);
 // Point the n chains in slots slot0.. at their next part: chain i's src becomes
 // addr[i * stride] - off (a HOST array, copied into the kernel arguments, one launch per 256
 // chains), off being the byte position in the chain at which that part starts. The ticks then

@@ -62,9 +62,13 @@ class HashQueue:
               "HashQueue")
         self._h = h
         self.capacity = capacity
+        self.device = device
+        self._kept = []  # (ticket, uploaded expectations) of the checking adds still live
 
     def close(self) -> None:
         if getattr(self, "_h", None):
+            if getattr(self, "_kept", None):
+                self._release(everything=True)
             _lib.load().cec_hashq_destroy(self._h)
             self._h = None
 
@@ -168,6 +172,115 @@ class HashQueue:
             raise bad from None
         return t.value
 
+    def _expect(self, expect, n: int):
+        """The recorded hashes of n chains as memory the device reads: a uint8 tensor [n][64]
+        (device or pinned host) as it is, a list of n 64-byte `bytes` uploaded once. Returns
+        (address, the uploaded tensor or None)."""
+        import torch
+        if isinstance(expect, torch.Tensor):
+            if expect.dtype != torch.uint8 or expect.numel() != n * 64 or \
+                    not expect.is_contiguous() or not (expect.is_cuda or expect.is_pinned()):
+                raise ErrInvalidInput("expect must be a contiguous device or pinned uint8 [n][64]")
+            return expect.data_ptr(), None
+        rows = [bytes(h) for h in expect]
+        if len(rows) != n or any(len(h) != 64 for h in rows):
+            raise ErrInvalidInput("expect must hold one 64-byte hash per chain")
+        host = torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.uint8)
+        up = host.to(torch.device("cuda", self.device))
+        return up.data_ptr(), up
+
+    def _ok(self, d_ok, n: int):
+        import torch
+        if d_ok is None:
+            d_ok = torch.empty(n, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        elif d_ok.numel() < n:
+            raise ErrShardSize(ErrShardSize.__doc__)
+        return d_ok
+
+    def _release(self, everything: bool = False) -> None:
+        """Drop the uploaded expectations of adds that are complete. A tensor is handed back to
+        the allocator marked as in use on the queue's stream, so its memory is reused only once
+        the ticks enqueued there have run."""
+        if not self._kept:
+            return
+        import torch
+        if self.stream is None:
+            s = torch.cuda.default_stream(self.device)
+        elif isinstance(self.stream, int):
+            s = torch.cuda.ExternalStream(self.stream, device=self.device)
+        else:
+            s = self.stream
+        live = []
+        for ticket, up in self._kept:
+            if everything or self.done(ticket):
+                up.record_stream(s)
+            else:
+                live.append((ticket, up))
+        self._kept = live
+
+    def add_check(self, d_base, n: int, per: int, outer_stride: int, inner_stride: int,
+                  length: int, d_expect, expect_outer: int, d_ok, ok_outer: int, d_hex=None,
+                  hex_outer: int = 0, expect_offset: int = 0, ok_offset: int = 0,
+                  hex_offset: int = 0) -> int:
+        """`add` whose chains are also checked on the GPU (cec_hashq_add_check): chain i compares
+        its digest with the 64 lowercase hex chars at
+        d_expect + expect_offset + ((i // per) * expect_outer + i % per) * 64 (memory the device
+        reads, 4-byte aligned: a device tensor, or the int address of e.g. a pinned host tensor)
+        and writes 1 (equal) or 0 to d_ok + ok_offset + (i // per) * ok_outer + i % per, in the
+        tick launch that completes it; nothing is preset. d_hex None: flags only. Returns the
+        add's ticket."""
+        t = c_uint64()
+        check(_lib.load().cec_hashq_add_check(self._h, _dev_ptr(d_base), n, per, outer_stride,
+                                              inner_stride, length, _at(d_expect, expect_offset),
+                                              expect_outer, _at(d_ok, ok_offset), ok_outer,
+                                              _at(d_hex, hex_offset), hex_outer, byref(t)),
+              "HashQueue.add_check")
+        return t.value
+
+    def add_check_ptrs(self, tensors, expect, d_ok=None, d_hex=None):
+        """`add_ptrs` with the check: one chain per tensor of `tensors` (1-D uint8 device tensors
+        of one length, wherever they lie), chain i compared with expect[i], its flag (1 equal, 0
+        not) written to d_ok[i] by the tick launch that completes it and its hex, with d_hex, to
+        d_hex + 64 * i. `expect`: a device or pinned uint8 tensor [n][64], or a list of n 64-byte
+        `bytes`, which is uploaded once and kept by the queue until the add is complete. d_ok
+        None: a new uint8 device tensor [n]. Nothing waits. Returns (ticket, d_ok)."""
+        return self.add_check_concat_ptrs([[t] for t in tensors], expect, d_ok, d_hex)
+
+    def add_check_concat_ptrs(self, chains, expect, d_ok=None, d_hex=None, d_prefix_hex=None,
+                              length: Optional[int] = None):
+        """`add_concat_ptrs` with the check (cec_hashq_add_check_concat_ptrs): one chain per row
+        of `chains` (a segment over its scattered data fragments), chain i compared with
+        expect[i] and flagged in d_ok[i] as in `add_check_ptrs`; the prefix digest stays a hex
+        output only. Rows of one tensor may be of any length. Returns (ticket, d_ok)."""
+        chains, flat, part_len = _rows(chains)
+        n = len(chains)
+        d_ok = self._ok(d_ok, n)
+        if n == 0:
+            return 0, d_ok
+        parts = len(chains[0])
+        if parts > 1 and part_len == 0:
+            raise ErrShardNoData(ErrShardNoData.__doc__)
+        exp, up = self._expect(expect, n)
+        ptrs = (c_void_p * max(1, len(flat)))(*[_dev_ptr(t) for t in flat])
+        t = c_uint64()
+        lib = _lib.load()
+        if length is None:  # one buffer per chain: len is its length as it is, 0 included
+            length = part_len if parts == 1 else 0
+        try:
+            check(lib.cec_hashq_add_check_concat_ptrs(self._h, ptrs, n, parts, part_len, length,
+                                                      exp, _dev_ptr(d_ok), _at(d_hex),
+                                                      _at(d_prefix_hex), byref(t)),
+                  "HashQueue.add_check_concat_ptrs")
+        except CecError as e:
+            if e.code != _lib.CEC_EINVAL or isinstance(e, ErrInvalidInput):
+                raise
+            bad = ErrInvalidInput(str(e))
+            bad.code = e.code
+            raise bad from None
+        if up is not None:
+            self._kept.append((t.value, up))
+        return t.value, d_ok
+
     def add_fragments(self, d_data, d_parity, nseg: int, k: int, m: int, shard_len: int,
                       d_hex, with_parity: bool = True) -> int:
         """Hash every fragment of a batch ([nseg][k][len] data, [nseg][m][len] parity) into
@@ -248,10 +361,12 @@ class HashQueue:
     def tick(self, max_blocks: int = 0) -> None:
         """Advance every live chain by at most max_blocks blocks (0: to completion)."""
         check(_lib.load().cec_hashq_tick(self._h, max_blocks), "HashQueue.tick")
+        self._release()
 
     def finish(self) -> None:
         """Enqueue ticks until every chain added so far is complete."""
         check(_lib.load().cec_hashq_finish(self._h), "HashQueue.finish")
+        self._release()
 
     def status(self, ticket: int = 0):
         done, live, left = c_int(), c_size_t(), c_uint64()

@@ -164,6 +164,29 @@ def repair_batch(enc: Encoder, d_data, d_parity, nseg: int, shard_len: int, pres
     return (ok, calls) if complete_calls else ok
 
 
+def check_batch_device(queue, d_data, d_parity, nseg: int, k: int, m: int, shard_len: int,
+                       expected: Sequence[Dict[int, bytes]]):
+    """The recorded-hash gate of `repair_batch` as flags in HBM: for a batch ([nseg][k][len] data,
+    [nseg][m][len] parity, rebuilt or not) and `expected` ([{fragment index: recorded hash}] per
+    segment), one chain per named fragment is added to `queue` (HashQueue.add_check_ptrs over
+    views of the batch) and ticked to completion there; each compares its SHA-256 with the
+    recorded hash on the GPU. Returns (d_ok, index): index is the host list of the (segment,
+    fragment index) pairs in `repair_batch`'s order, d_ok[j] is 1 where fragment index[j] hashes
+    to its recorded value, else 0. Nothing is copied out or waited for: the flags are final when
+    the queue's stream gets there."""
+    if len(expected) != nseg:
+        raise ValueError("expected needs one dict per segment")
+    which = [(s, i, bytes(h)) for s in range(nseg) for i, h in expected[s].items()]
+    if any(not 0 <= i < k + m for _, i, _ in which):
+        raise ValueError("fragment index out of range")
+    frags = [d_data[s, i] if i < k else d_parity[s, i - k] for s, i, _ in which]
+    if any(t.numel() != shard_len for t in frags):
+        raise ValueError("shard_len does not match the batch")
+    _, d_ok = queue.add_check_ptrs(frags, [h for _, _, h in which])
+    queue.finish()
+    return d_ok, [(s, i) for s, i, _ in which]
+
+
 def generate_fillers(n: int, seed: int = 0xF111E5, filler_size: int = geometry.FRAGMENT_SIZE,
                      first: int = 0, device: int = 0, hash_on: str = "auto",
                      hash_threads: int = 16):

@@ -472,6 +472,41 @@ int cec_hashq_add_ptrs(cec_hashq* q, const uint8_t* const* d_bufs, size_t n, siz
 int cec_hashq_add_concat_ptrs(cec_hashq* q, const uint8_t* const* d_parts, size_t n, size_t parts,
                               size_t part_len, size_t len, uint8_t* d_hex, uint8_t* d_prefix_hex,
                               uint64_t* ticket);
+/* cec_hashq_add whose chains are also checked: chain i compares its digest with the 64 lowercase hex
+ * chars at d_expect + ((i / per) * expect_outer + i % per) * 64 and writes 1 (equal) or 0 to
+ * d_ok[(i / per) * ok_outer + i % per]. d_hex may be NULL (flags only). The recorded-hash check of
+ * a scrub, a repair gate or a retrieval, left in HBM on the queue's stream like the flags of
+ * cec_verify_ptrs: no hex to copy out, nothing to wait for. d_expect is memory the device reads
+ * (device memory or pinned host memory, as d_states of cec_hashq_add_resume), 4-byte aligned; it is
+ * read by the tick launch that completes the chain, so it stays valid until the add is complete.
+ * d_ok is device memory of any alignment. The 64 bytes are compared as bytes with the lowercase
+ * hex the queue would have written; the queue does not parse them, so an upper-case or non-hex
+ * expectation is a mismatch (flag 0), not an error. A flag is written exactly once, by the launch
+ * that completes its chain: nothing is preset (unlike cec_verify_ptrs; a caller who wants one
+ * flag per segment over several fragments ANDs them) and no other byte of d_ok is touched. The
+ * chains join the ring like those of any add: same ticket and status bookkeeping, every tick
+ * mode. Checked before anything is enqueued (on an error the ring is unchanged and no byte is
+ * written): CEC_EINVAL for d_expect or d_ok NULL with n > 0 (a caller without expectations uses
+ * cec_hashq_add), a d_expect that is not 4-byte aligned, and whatever cec_hashq_add refuses;
+ * CEC_ENOMEM when the ring would overflow (nothing is added). n == 0: CEC_OK, ticket 0. */
+int cec_hashq_add_check(cec_hashq* q, const uint8_t* d_base, size_t n, size_t per,
+                        size_t outer_stride, size_t inner_stride, size_t len,
+                        const uint8_t* d_expect, size_t expect_outer, uint8_t* d_ok, size_t ok_outer,
+                        uint8_t* d_hex, size_t hex_outer, uint64_t* ticket);
+/* cec_hashq_add_concat_ptrs (parts == 1: cec_hashq_add_ptrs) with the check: chain i against
+ * d_expect + 64 * i, flag to d_ok + i. d_hex, d_prefix_hex as there, either may be NULL. A miner's
+ * stored fragments scrubbed against their recorded hashes (parts == 1), a segment over its
+ * scattered data fragments against its segment hash. d_expect, d_ok, the comparison and the flag
+ * writes are those of cec_hashq_add_check; the prefix digest stays a hex output and is not
+ * checked. With parts == 1 and no d_prefix_hex the call is cec_hashq_add_ptrs: part_len is not
+ * used and len is every buffer's length as it is, 0 included. Checked before anything is
+ * enqueued (on an error the ring is unchanged and no byte is written): CEC_EINVAL for d_expect or
+ * d_ok NULL with n > 0, a d_expect that is not 4-byte aligned, and whatever the form it extends
+ * refuses; CEC_ENOMEM when the ring would overflow. n == 0: CEC_OK, ticket 0. */
+int cec_hashq_add_check_concat_ptrs(cec_hashq* q, const uint8_t* const* d_parts, size_t n,
+                                    size_t parts, size_t part_len, size_t len,
+                                    const uint8_t* d_expect, uint8_t* d_ok, uint8_t* d_hex,
+                                    uint8_t* d_prefix_hex, uint64_t* ticket);
 /* Advance every live chain by at most max_blocks 64-byte blocks (0 = to completion). */
 int cec_hashq_tick(cec_hashq* q, uint32_t max_blocks);
 /* Tick until every chain added so far is complete (enqueued; synchronise the stream to wait). */

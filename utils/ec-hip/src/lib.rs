@@ -228,6 +228,16 @@ pub mod sys {
                                          parts: usize, part_len: usize, len: usize,
                                          d_hex: *mut u8, d_prefix_hex: *mut u8,
                                          ticket: *mut u64) -> c_int;
+        pub fn cec_hashq_add_check(q: *mut cec_hashq, d_base: *const u8, n: usize, per: usize,
+                                   outer_stride: usize, inner_stride: usize, len: usize,
+                                   d_expect: *const u8, expect_outer: usize, d_ok: *mut u8,
+                                   ok_outer: usize, d_hex: *mut u8, hex_outer: usize,
+                                   ticket: *mut u64) -> c_int;
+        pub fn cec_hashq_add_check_concat_ptrs(q: *mut cec_hashq, d_parts: *const *const u8,
+                                               n: usize, parts: usize, part_len: usize,
+                                               len: usize, d_expect: *const u8, d_ok: *mut u8,
+                                               d_hex: *mut u8, d_prefix_hex: *mut u8,
+                                               ticket: *mut u64) -> c_int;
         pub fn cec_hashq_tick(q: *mut cec_hashq, max_blocks: u32) -> c_int;
         pub fn cec_hashq_finish(q: *mut cec_hashq) -> c_int;
         pub fn cec_hashq_status(q: *const cec_hashq, ticket: u64, done: *mut c_int,
@@ -758,6 +768,30 @@ pub unsafe fn hashq_add_concat_ptrs(q: *mut sys::cec_hashq, d_parts: &[*const u8
     let mut ticket = 0u64;
     check(sys::cec_hashq_add_concat_ptrs(q, d_parts.as_ptr(), d_parts.len() / parts, parts,
                                          part_len, len, d_hex, d_prefix_hex, &mut ticket))?;
+    Ok(ticket)
+}
+
+/// `hashq_add_concat_ptrs` whose chains are checked against their recorded hashes on the GPU
+/// (`cec_hashq_add_check_concat_ptrs`; `parts == 1`: one buffer per chain, a miner's scrub): chain
+/// i compares its digest with the 64 lowercase hex chars at `d_expect + 64 * i` and writes 1
+/// (equal) or 0 to `d_ok + i`, in the tick launch that completes it. `d_hex` and `d_prefix_hex`
+/// may be null (flags only). Returns the add's ticket.
+///
+/// # Safety
+/// As `hashq_add_concat_ptrs`; `d_expect` must be memory the device reads (64 bytes per chain,
+/// 4-byte aligned) and `d_ok` device memory (one byte per chain), both valid until the add is
+/// complete.
+pub unsafe fn hashq_add_check_concat_ptrs(q: *mut sys::cec_hashq, d_parts: &[*const u8],
+                                          parts: usize, part_len: usize, len: usize,
+                                          d_expect: *const u8, d_ok: *mut u8, d_hex: *mut u8,
+                                          d_prefix_hex: *mut u8) -> Result<u64, Error> {
+    if parts == 0 || d_parts.len() % parts != 0 {
+        return Err(Error::from_code(CEC_EINVAL));
+    }
+    let mut ticket = 0u64;
+    check(sys::cec_hashq_add_check_concat_ptrs(q, d_parts.as_ptr(), d_parts.len() / parts, parts,
+                                               part_len, len, d_expect, d_ok, d_hex,
+                                               d_prefix_hex, &mut ticket))?;
     Ok(ticket)
 }
 
