@@ -5,6 +5,7 @@ this package is the host-side mirror of the off-chain codec API (klauspost/reeds
 plus the CESS segment / fragment records.
 """
 from . import audit, geometry, records
+from ._lib import CEC_FLAG_CLEAN, CEC_FLAG_LOST, CEC_FLAG_MANY, CEC_FLAG_REBUILT
 from .hashq import HashQueue, sha256_blocks
 from .records import ErrTooManySegments
 from .reedsolomon import (
@@ -22,6 +23,7 @@ from .reedsolomon import (
     New,
     decode_rows,
     fill_synthetic,
+    flag_status,
     sha256_hex_device,
     sha256_hex_host,
     xor_batch,
@@ -32,5 +34,6 @@ __all__ = [
     "ErrReconstructRequired", "ErrShardNoData", "ErrShardSize", "ErrShortData",
     "ErrTooFewShards", "HipError", "fill_synthetic", "sha256_hex_device", "sha256_hex_host",
     "HashQueue", "sha256_blocks", "records", "ErrTooManySegments", "audit", "xor_batch",
-    "ErrInvalidInput", "decode_rows",
+    "ErrInvalidInput", "decode_rows", "flag_status", "CEC_FLAG_CLEAN", "CEC_FLAG_REBUILT",
+    "CEC_FLAG_MANY", "CEC_FLAG_LOST",
 ]

@@ -84,6 +84,10 @@ SIGNATURES = {
                                              c_void_p]),
     "cec_xor_ptrs": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_size_t, c_size_t,
                              c_size_t, c_void_p]),
+    "cec_flag_status": (c_int, [c_int, c_int, POINTER(c_uint8), POINTER(c_uint8),
+                                POINTER(c_int), POINTER(c_int)]),
+    "cec_repair_flagged_ptrs": (c_int, [c_void_p, POINTER(c_void_p), c_void_p, c_size_t,
+                                        c_size_t, c_void_p, c_void_p]),
     "cec_encode_idx_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_size_t,
                                      c_size_t, c_int, c_void_p]),
     "cec_update_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,
@@ -223,6 +227,10 @@ CEC_STAT_RETIRED_PENDING = 2
 CEC_STAT_POOL_BYTES = 3
 CEC_STAT_FFTDEC_SEGMENTS = 4
 CEC_STAT_FFTDEC_D_SEGMENTS = 5
+CEC_FLAG_CLEAN = 0
+CEC_FLAG_REBUILT = 1
+CEC_FLAG_MANY = 2
+CEC_FLAG_LOST = 3
 CEC_HQOPT_TICK = 1
 CEC_PIPE_HASH_NONE = 0
 CEC_PIPE_HASH_GPU = 1

@@ -129,3 +129,63 @@ def scrub_device(frags: Sequence, recorded, queue=None, d_ok=None):
         _, d_ok = q.add_check_ptrs(frags, recorded, d_ok)
         q.finish()
     return d_ok
+
+
+def scrub_repair_device(enc: Encoder, segments: Sequence, recorded, queue=None):
+    """A miner's scrub that heals what it finds, without a host round trip: `segments` is a list
+    of lists of k + m 1-D uint8 device tensors of one length (None = not held), `recorded` their
+    hashes, per segment a list of k + m 64-byte `bytes` (anything at a shard not held), or one
+    uint8 device / pinned tensor [nseg][k + m][64]. All on `queue`'s stream, nothing waited for:
+    every held fragment gets a checked chain (HashQueue.add_check_ptrs, segment-major, the flag of
+    fragment i of segment s at d_flags[s][i]; slots not held get no chain and their flag byte is
+    whatever the buffer held, which the repair ignores), the queue is ticked to completion
+    (finish()), and Encoder.RepairFlaggedDevice reads the flags where the ticks left them: a
+    segment with exactly one fragment that no longer hashes to its record, and at least k that
+    do, has that fragment rebuilt in place from the others. Returns (d_flags [nseg][k + m],
+    d_status [nseg] of CEC_FLAG_* codes), both final when the stream gets there. The rebuild is
+    not re-checked: a caller who wants proof scrubs again (a fragment whose *record* is wrong is
+    rebuilt to the same bytes and flagged again). queue None: a queue of the call's size on
+    torch's current stream, owned and closed by the call, as in scrub_device."""
+    import torch
+    from .hashq import HashQueue
+    segments = [list(seg) for seg in segments]
+    nseg, n = len(segments), enc.Shards
+    if any(len(seg) != n for seg in segments):
+        raise ErrInvalidInput(ErrInvalidInput.__doc__)
+    dev = torch.device("cuda", enc.device)
+    slots = [t for seg in segments for t in seg]
+    d_flags = torch.empty((nseg, n), dtype=torch.uint8, device=dev)
+    if isinstance(recorded, torch.Tensor):
+        if recorded.numel() != nseg * n * 64:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        rec = recorded.view(nseg * n, 64)
+    else:
+        rec = [h for row in recorded for h in row]
+        if len(rec) != nseg * n:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+    # one add per run of held slots: its flags land at the run's place in d_flags
+    runs, a = [], 0
+    while a < len(slots):
+        if slots[a] is None:
+            a += 1
+            continue
+        b = a
+        while b < len(slots) and slots[b] is not None:
+            b += 1
+        runs.append((a, b))
+        a = b
+
+    def go(q):
+        flat = d_flags.view(-1)
+        for a, b in runs:
+            q.add_check_ptrs(slots[a:b], rec[a:b], flat[a:b])
+        q.finish()
+        stream = q.stream if q.stream is not None else 0  # a queue without one: the null stream
+        return enc.RepairFlaggedDevice(segments, d_flags, stream=stream)
+
+    if queue is not None:
+        return d_flags, go(queue)
+    held = sum(b - a for a, b in runs)
+    cap = 1 << max(0, held - 1).bit_length()
+    with HashQueue(capacity=cap, device=enc.device, stream=torch.cuda.current_stream(dev)) as q:
+        return d_flags, go(q)

@@ -1824,6 +1824,156 @@ int cec_xor_ptrs(cec_codec* c, uint8_t* const* dst, const uint8_t* const* src, s
                        });
 }
 
+static_assert(CEC_FLAG_CLEAN == cec::kFlagClean && CEC_FLAG_REBUILT == cec::kFlagRebuilt &&
+                  CEC_FLAG_MANY == cec::kFlagMany && CEC_FLAG_LOST == cec::kFlagLost,
+              "the planner kernels write the header's codes");
+
+int cec_flag_status(int k, int m, const uint8_t* held, const uint8_t* flags, int* status,
+                    int* lost) {
+  if (!held || !flags || !status) return set_err(CEC_EINVAL, "null");
+  if (k < 1 || m < 1 || k + m > cec::kMaxShards)
+    return set_err(CEC_EINVAL, "need k >= 1, m >= 1, k + m <= 256");
+  int bad = 0, good = 0, first = -1;
+  for (int i = 0; i < k + m; ++i) {
+    if (!held[i]) continue;
+    if (flags[i]) {
+      ++good;
+    } else if (bad++ == 0) {
+      first = i;
+    }
+  }
+  *status = bad == 0 ? CEC_FLAG_CLEAN
+            : good < k ? CEC_FLAG_LOST
+            : bad == 1 ? CEC_FLAG_REBUILT
+                       : CEC_FLAG_MANY;
+  if (lost) *lost = *status == CEC_FLAG_REBUILT ? first : -1;
+  return CEC_OK;
+}
+
+// cec_repair_flagged_ptrs: which shard of a segment is rebuilt is decided on the device, from
+// flags that may not exist yet when this returns, so the host prepares every answer. Segments are
+// grouped by held set; for a group that holds more than k shards, every held shard j gets the
+// program cec_reconstruct_ptrs would use for (held \ {j}, required {j}). The planner kernel
+// (kernels.h FlagPlan) picks per segment and writes the working table; the product launches
+// behind it cover every segment and leave at once where the planner wrote an idle row. Nothing
+// here waits for `st` or copies from the device. RS(2,1)'s compile-time rows need no program.
+static int repair_flagged_impl(cec_codec* c, uint8_t* const* shards, const uint8_t* d_flags,
+                               size_t nseg, size_t shard_len, uint8_t* d_status, hipStream_t st) {
+  const int n = c->k + c->m, k = c->k;
+  const bool ct21 = k == 2 && c->m == 1 && !c->force_generic;
+  const uint32_t rs = ct21 ? 4u : (uint32_t)k + 2;
+  // any shard may become a destination: the same address twice is two rows that may race
+  std::unordered_set<uintptr_t> seen;
+  uintptr_t bits = 0;  // OR of every held address: the alignment of the call
+  for (size_t i = 0; i < nseg * n; ++i) {
+    if (!shards[i]) continue;
+    if (!seen.insert((uintptr_t)shards[i]).second)
+      return set_err(CEC_EINVAL, "a shard address is named twice");
+    bits |= (uintptr_t)shards[i];
+  }
+  const bool vec_ok = (bits & 15) == 0;
+  struct Group {
+    std::vector<ProgPtr> progs;  // by lost shard; null where the held set cannot lose that one
+  };
+  std::unordered_map<std::string, size_t> gidx;
+  std::vector<Group> groups;
+  Uploads up{c->stream, c->arena};  // synchronised once, with the table's upload
+  std::string key((size_t)n, '\0');
+  // the upload: [nseg][n + 1] addresses and group, [group][n] chunks, [group][n][k] survivors
+  std::vector<uint64_t> host(nseg * (n + 1), 0);
+  bool any_prog = false;
+  for (size_t s = 0; s < nseg; ++s) {
+    int nheld = 0;
+    for (int i = 0; i < n; ++i) {
+      host[s * (n + 1) + i] = (uint64_t)(uintptr_t)shards[s * n + i];
+      key[i] = shards[s * n + i] ? 1 : 0;
+      nheld += key[i];
+    }
+    if (ct21) continue;  // one group, no programs
+    const size_t gi = group_of(gidx, key, groups.size());
+    host[s * (n + 1) + n] = gi;
+    if (gi < groups.size()) continue;
+    groups.push_back({std::vector<ProgPtr>(n)});
+    if (nheld <= k) continue;  // one bad shard leaves fewer than k: nothing can be rebuilt
+    uint8_t present[cec::kMaxShards], required[cec::kMaxShards] = {};
+    for (int i = 0; i < n; ++i) present[i] = (uint8_t)key[i];
+    for (int j = 0; j < n; ++j) {
+      if (!key[j]) continue;
+      present[j] = 0;
+      required[j] = 1;
+      ProgPtr p;
+      const int rc = get_decode(c, present, false, &p, &up.arena, required);
+      present[j] = 1;
+      required[j] = 0;
+      if (rc) return rc;
+      if (p->nout != 1 || p->chunks.size() != 1 || p->chunks[0].nob != 1 ||
+          p->chunks[0].nin != k || p->out_idx[0] != j)
+        return set_err(CEC_EINVAL, "a one-shard rebuild is not one chunk of one output");
+      groups.back().progs[j] = std::move(p);
+      any_prog = true;
+    }
+  }
+  const size_t ng = groups.size();
+  const size_t chunks_at = host.size(), surv_at = chunks_at + ng * n;
+  const size_t in_words = surv_at + (ng * n * k + 7) / 8;
+  host.resize(in_words, 0);
+  uint8_t* surv = reinterpret_cast<uint8_t*>(host.data() + surv_at);
+  for (size_t g = 0; g < ng; ++g)
+    for (int j = 0; j < n; ++j) {
+      const ProgPtr& p = groups[g].progs[j];
+      if (!p) continue;
+      host[chunks_at + g * n + j] = (uint64_t)(uintptr_t)p->chunks[0].dev;
+      std::memcpy(surv + (g * n + j) * k, p->in_idx, k);
+    }
+  void* d = nullptr;
+  const size_t in_bytes = in_words * sizeof(uint64_t);
+  const size_t bytes = in_bytes + nseg * rs * sizeof(uint64_t);
+  int rc = c->pool.alloc(bytes, &d);
+  if (rc) return rc;
+  hipError_t e = hipMemcpyAsync(d, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the programs' uploads too
+  up.arena.reset();
+  if (e != hipSuccess) {
+    c->pool.retire(d, bytes);
+    return set_err(CEC_EHIP, std::string("table upload: ") + hipGetErrorString(e));
+  }
+  uint64_t* dw = static_cast<uint64_t*>(d);
+  cec::FlagPlan fp{};
+  fp.segs = dw;
+  fp.chunks = dw + chunks_at;
+  fp.surv = reinterpret_cast<const uint8_t*>(dw + surv_at);
+  fp.flags = d_flags;
+  fp.status = d_status;
+  fp.rows = dw + in_words;
+  fp.nseg = (uint32_t)nseg;
+  fp.n = n;
+  fp.k = k;
+  cec::launch_flag_plan(fp, ct21, st);
+  rc = check_launch();
+  if (!rc && ct21) {
+    cec::launch_ptrs_rs21(cec::PtrSink::store, fp.rows, fp.nseg, shard_len, vec_ok, nullptr, st);
+    rc = check_launch();
+  } else if (!rc && any_prog) {  // without a program every row is idle
+    cec::launch_ptrs_rt_flag(cec::rt_takes_rtb(c->opts, 1, k), fp.rows, fp.nseg, rs, shard_len,
+                             vec_ok, st);
+    rc = check_launch();
+  }
+  const int mrc = c->pool.mark(st);  // the table and the programs stay until these complete
+  c->pool.retire(d, bytes);
+  evict_decode(c);  // `groups` holds the call's programs to the end
+  return rc ? rc : mrc;
+}
+
+int cec_repair_flagged_ptrs(cec_codec* c, uint8_t* const* shards, const uint8_t* d_flags,
+                            size_t nseg, size_t shard_len, uint8_t* d_status, void* hip_stream) {
+  if (!c || (nseg && (!shards || !d_flags || !d_status))) return set_err(CEC_EINVAL, "null");
+  if (int rc = check_batch(nseg, shard_len)) return rc;
+  if (nseg == 0) return CEC_OK;
+  CEC_HIP_TRY(hipSetDevice(c->device));
+  return repair_flagged_impl(c, shards, d_flags, nseg, shard_len, d_status,
+                             pick_stream(c, hip_stream));
+}
+
 int cec_reconstruct_partial_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size_t nseg,
                                   size_t shard_len, const uint8_t* present, const uint8_t* held,
                                   int data_only, void* hip_stream) {

@@ -157,6 +157,35 @@ void launch_ptrs_rs21(PtrSink sink, const uint64_t* tab, uint32_t nrows, uint64_
 void launch_ptrs_rt(PtrSink sink, bool bitplane, const uint64_t* tab, uint32_t nrows, uint32_t rs,
                     int nob, uint64_t len, bool vec_ok, uint8_t* ok, hipStream_t st);
 
+// Rebuilds decided on the GPU (cec_repair_flagged_ptrs): a planner kernel reads per-fragment flags
+// from device memory and writes the rows of the table above, which the next launches on the
+// stream run. The per-segment rule is cec_flag_status's (cess_ec.h): bad = held and flag == 0,
+// good = held and flag != 0; no bad: clean; one bad and >= k good: rebuilt; two or more bad and
+// >= k good: many; else lost. The codes are the CEC_FLAG_* values.
+enum : uint32_t { kFlagClean = 0, kFlagRebuilt = 1, kFlagMany = 2, kFlagLost = 3 };
+struct FlagPlan {
+  const uint64_t* segs;    // [nseg][n + 1]: a segment's n shard addresses (0: not held), then the
+                           // index of its group (segments of one held set)
+  const uint64_t* chunks;  // [group][n]: the program chunk that rebuilds shard j of the group's
+                           // held set from the others (0: none; unused for RS(2,1) rows)
+  const uint8_t* surv;     // [group][n][k]: that program's survivors, shard indices in its order
+  const uint8_t* flags;    // [nseg][n], any alignment; bytes of shards not held are not read
+  uint8_t* status;         // [nseg]: kFlag* per segment
+  uint64_t* rows;          // the working table, row s for segment s (no compaction: the table
+                           // does not depend on the order in which waves run)
+  uint32_t nseg;
+  int n, k;
+};
+// rs21: rows {input 0, input 1, output, case} for launch_ptrs_rs21, a segment that is not rebuilt
+// gets {0, 0, 0, 3}, a case k_ptr21 leaves without touching an address (n == 3, one lane per
+// segment). Otherwise rows {program chunk, k inputs, 1 output}, k + 2 words, for
+// launch_ptrs_rt_flag, a segment that is not rebuilt gets an all-zero row (one wave per segment).
+void launch_flag_plan(const FlagPlan& p, bool rs21, hipStream_t st);
+// launch_ptrs_rt's store form for one-output chunks (nob == 1) over rows a planner wrote: a row
+// whose word 0 is zero is left before its program chunk or any of its addresses is looked at.
+void launch_ptrs_rt_flag(bool bitplane, const uint64_t* tab, uint32_t nrows, uint32_t rs,
+                         uint64_t len, bool vec_ok, hipStream_t st);
+
 // SHA-256 of `n` equal-length buffers, written as 64 lowercase hex characters each into
 // `hex_out` (device, n * 64 bytes). If `ptrs` is null, buffer i is shard (i % nshards) of
 // segment (i / nshards) in layout L.

@@ -1912,6 +1912,90 @@ __global__ __launch_bounds__(256) void k_ptrb(const uint64_t* __restrict__ tab, 
       row_sink<Sink>([&]() CEC_AI { return tab_row(tab, r, rs)[rs - 1]; }, sa...));
 }
 
+// The flag forms (cec_repair_flagged_ptrs): the same products over rows that a planner kernel
+// wrote earlier on the stream, where a segment with nothing to rebuild has an all-zero row. Word 0
+// (the program chunk) is looked at first and a zero ends the workgroup there: TableAddr reads the
+// chunk's header and the bodies load input 0 whatever the program says.
+template <int NOB, int U, class TV>
+__global__ __launch_bounds__(256) void k_ptrt_flag(const uint64_t* __restrict__ tab, uint32_t row0,
+                                                   uint32_t rs, uint64_t len, int vec_ok) {
+  const uint64_t r = row0 + blockIdx.y;
+  if (tab_row(tab, r, rs)[0] == 0) return;
+  rt_body<NOB, U, TV, TableAddr>(TableAddr(tab, r, rs, len), vec_ok, StoreSink{});
+}
+
+template <int NOB, class TV, int PF>
+__global__ __launch_bounds__(256) void k_ptrb_flag(const uint64_t* __restrict__ tab, uint32_t row0,
+                                                   uint32_t rs, uint64_t len, int vec_ok) {
+  const uint64_t r = row0 + blockIdx.y;
+  if (tab_row(tab, r, rs)[0] == 0) return;
+  rtb_body<NOB, TV, PF, TableAddr>(TableAddr(tab, r, rs, len), vec_ok, StoreSink{});
+}
+
+// The planners (kernels.h FlagPlan): what to rebuild is read from flags in HBM and turned into
+// the rows above. Row s is segment s's, written whole whatever its status, with plain stores; the
+// products read it through the constant address space in a later launch.
+__device__ __forceinline__ uint32_t flag_status(uint32_t nbad, uint32_t ngood, uint32_t k) {
+  return nbad == 0 ? kFlagClean : ngood < k ? kFlagLost : nbad == 1 ? kFlagRebuilt : kFlagMany;
+}
+
+// RS(2,1): one lane per segment. Rebuilding shard j reads the other two in index order, which is
+// k_ptr21's case j.
+__global__ __launch_bounds__(256) void k_flag_plan21(FlagPlan p) {
+  const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s >= p.nseg) return;
+  const uint64_t* __restrict__ seg = p.segs + s * 4;
+  const uint8_t* __restrict__ fl = p.flags + s * 3;
+  const uint64_t a0 = seg[0], a1 = seg[1], a2 = seg[2];
+  const bool g0 = a0 && fl[0], g1 = a1 && fl[1], g2 = a2 && fl[2];
+  const bool b0 = a0 && !g0, b1 = a1 && !g1, b2 = a2 && !g2;
+  const uint32_t st = flag_status(b0 + b1 + b2, g0 + g1 + g2, 2);
+  p.status[s] = (uint8_t)st;
+  uint64_t* __restrict__ row = p.rows + s * 4;
+  const bool go = st == kFlagRebuilt;
+  const uint32_t j = b0 ? 0 : b1 ? 1 : 2;
+  row[0] = !go ? 0 : j == 0 ? a1 : a0;
+  row[1] = !go ? 0 : j == 2 ? a1 : a2;
+  row[2] = !go ? 0 : j == 0 ? a0 : j == 1 ? a1 : a2;
+  row[3] = go ? j : 3;
+}
+
+// Any code: one wave per segment, four segments per workgroup. The lanes stride over the n flags
+// (ballots give the counts and the first bad index, which is the bad index when it matters), then
+// over the k survivor addresses of the program for that index.
+__global__ __launch_bounds__(256) void k_flag_plan(FlagPlan p) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t s = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= p.nseg) return;  // the whole wave
+  const uint32_t n = (uint32_t)p.n, k = (uint32_t)p.k;
+  const uint64_t* __restrict__ seg = p.segs + s * (n + 1);
+  const uint8_t* __restrict__ fl = p.flags + s * n;
+  uint32_t nbad = 0, ngood = 0, lost = 0;
+  for (uint32_t base = 0; base < n; base += 64) {
+    const uint32_t i = base + lane;
+    const bool held = i < n && seg[i] != 0;
+    const bool good = held && fl[i] != 0;
+    const unsigned long long bad = __ballot(held && !good);
+    if (bad && !nbad) lost = base + (uint32_t)__ffsll(bad) - 1;
+    nbad += (uint32_t)__popcll(bad);
+    ngood += (uint32_t)__popcll(__ballot(good));
+  }
+  const uint32_t st = flag_status(nbad, ngood, k);
+  if (lane == 0) p.status[s] = (uint8_t)st;
+  uint64_t* __restrict__ row = p.rows + s * (k + 2);
+  if (st != kFlagRebuilt) {
+    for (uint32_t t = lane; t < k + 2; t += 64) row[t] = 0;
+    return;
+  }
+  const uint64_t gj = seg[n] * n + lost;
+  const uint8_t* __restrict__ sv = p.surv + gj * k;
+  for (uint32_t t = lane; t < k; t += 64) row[1 + t] = seg[sv[t]];
+  if (lane == 0) {
+    row[0] = p.chunks[gj];
+    row[1 + k] = seg[lost];
+  }
+}
+
 namespace {
 // A launch's sink as a type: f(SinkTag<Sink>, the sink's kernel arguments...).
 template <class Sink>
@@ -1958,6 +2042,35 @@ void launch_ptrs_rt(PtrSink sink, bool bitplane, const uint64_t* tab, uint32_t n
                   nrows, st, rs, len, v, sa...);
     });
   });
+}
+
+void launch_ptrs_rt_flag(bool bitplane, const uint64_t* tab, uint32_t nrows, uint32_t rs,
+                         uint64_t len, bool vec_ok, hipStream_t st) {
+  const int v = vec_ok ? 1 : 0;
+  // the one-output bucket's shapes, as launch_ptrs_rt picks them
+  if (bitplane) {
+    rtb_dispatch(1, [&]<int NOB, class TV, int PF>(RtbShape<NOB, TV, PF>) {
+      if constexpr (NOB == 1)
+        launch_rows(k_ptrb_flag<NOB, TV, PF>, rt_grid_x(len, sizeof(TV), 1, vec_ok), tab, nrows, st,
+                    rs, len, v);
+    });
+    return;
+  }
+  rt_dispatch(1, [&]<int NOB, int U, class TV>(RtShape<NOB, U, TV>) {
+    if constexpr (NOB == 1)
+      launch_rows(k_ptrt_flag<NOB, U, TV>, rt_grid_x(len, sizeof(TV), U, vec_ok), tab, nrows, st,
+                  rs, len, v);
+  });
+}
+
+void launch_flag_plan(const FlagPlan& p, bool rs21, hipStream_t st) {
+  if (p.nseg == 0) return;
+  if (rs21)
+    hipLaunchKernelGGL(k_flag_plan21, dim3((unsigned)(((uint64_t)p.nseg + 255) / 256)), dim3(256), 0,
+                       st, p);
+  else
+    hipLaunchKernelGGL(k_flag_plan, dim3((unsigned)(((uint64_t)p.nseg + 3) / 4)), dim3(256), 0,
+                       st, p);
 }
 
 }  // namespace cec

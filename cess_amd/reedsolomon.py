@@ -472,6 +472,50 @@ class Encoder:
                                             self._device_stream(stream)), "VerifyDeviceBatch")
         return d_ok
 
+    def RepairFlaggedDevice(self, segments: Sequence, d_flags, d_status=None, stream=None):
+        """Heal flagged fragments in place (cec_repair_flagged_ptrs): `segments` is a list of
+        lists of k + m 1-D uint8 device tensors (None = not held), `d_flags` a uint8 device tensor
+        [nseg, k + m] where 0 marks a held shard as bad (what HashQueue.add_check_ptrs writes for
+        fragments listed segment-major; bytes of shards not held are ignored). The decision is
+        taken per segment on the GPU: a segment with exactly one bad shard and at least k good
+        ones gets that shard rebuilt over its tensor; every other segment is left as it is.
+        Returns the uint8 device tensor of len(segments) CEC_FLAG_* codes (flag_status states the
+        rule), `d_status` if given. Every tensor must be contiguous and on the codec's GPU
+        (TypeError for a shard, ErrInvalidInput for `d_flags` / `d_status`, and for a codec
+        without parity shards, which can heal nothing). Enqueued on `stream`
+        (default: torch's current stream) and not waited for, and no flag is copied to the host:
+        the flags may still be in production by work queued earlier on that stream."""
+        import torch
+        nseg, n = len(segments), self.Shards
+        dev = torch.device("cuda", self.device)
+        if (d_flags.dtype != torch.uint8 or d_flags.numel() != nseg * n or d_flags.device != dev
+                or not d_flags.is_contiguous()):
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        if d_status is None:
+            d_status = torch.empty(nseg, dtype=torch.uint8, device=dev)
+        elif (d_status.dtype != torch.uint8 or d_status.dim() != 1 or d_status.numel() != nseg
+              or d_status.device != dev or not d_status.is_contiguous()):
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        if nseg == 0:
+            return d_status
+        if self.ParityShards == 0:  # no parity, no codec: nothing could ever be rebuilt
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        ptrs = (c_void_p * (nseg * n))()
+        held = []
+        for s, shards in enumerate(segments):
+            if len(shards) != n:
+                raise ErrTooFewShards(ErrTooFewShards.__doc__)
+            for i, t in enumerate(shards):
+                if t is None:
+                    continue
+                held.append(_on_gpu(t, dev))
+                ptrs[s * n + i] = _dev_ptr(t)
+        size = self._check_device_shards(held)
+        check(self._lib.cec_repair_flagged_ptrs(self._h, ptrs, _dev_ptr(d_flags), nseg, size,
+                                                _dev_ptr(d_status), self._device_stream(stream)),
+              "RepairFlaggedDevice")
+        return d_status
+
     def ReconstructPartialDevice(self, shards: Sequence, present, out=None,
                                  accumulate: bool = False, stream=None) -> dict:
         """Partial rebuild of one segment in place (cec_reconstruct_partial_ptrs). `shards` is a
@@ -855,6 +899,23 @@ def decode_rows(data_shards: int, parity_shards: int, present, required):
                                       r.ctypes.data_as(u8p), rows.ctypes.data_as(u8p),
                                       idx.ctypes.data_as(u8p), byref(nreq)), "decode_rows")
     return idx[:nreq.value].copy(), rows[:nreq.value].copy()
+
+
+def flag_status(data_shards: int, parity_shards: int, held, flags):
+    """Host only (cec_flag_status): the rule RepairFlaggedDevice applies to one segment on the
+    GPU. `held` and `flags` are k+m values each (a held shard whose flag is 0 is bad). Returns
+    (CEC_FLAG_* status, the index of the shard a REBUILT segment rewrites or -1)."""
+    n = data_shards + parity_shards
+    h = np.ascontiguousarray(np.asarray(held, dtype=np.uint8))
+    f = np.ascontiguousarray(np.asarray(flags, dtype=np.uint8))
+    if h.shape != (n,) or f.shape != (n,):
+        raise ValueError("held and flags must have k+m values")
+    status, lost = c_int(-1), c_int(-2)
+    u8p = POINTER(c_uint8)
+    check(_lib.load().cec_flag_status(data_shards, parity_shards, h.ctypes.data_as(u8p),
+                                      f.ctypes.data_as(u8p), byref(status), byref(lost)),
+          "flag_status")
+    return status.value, lost.value
 
 
 def fill_synthetic(d_out, seg_bytes: int, nseg: int, seg0: int, seed: int, stream=None) -> None:

@@ -173,7 +173,8 @@ def check_batch_device(queue, d_data, d_parity, nseg: int, k: int, m: int, shard
     recorded hash on the GPU. Returns (d_ok, index): index is the host list of the (segment,
     fragment index) pairs in `repair_batch`'s order, d_ok[j] is 1 where fragment index[j] hashes
     to its recorded value, else 0. Nothing is copied out or waited for: the flags are final when
-    the queue's stream gets there."""
+    the queue's stream gets there. To act on such flags without reading them, rebuilding the
+    fragment that fails its check, see audit.scrub_repair_device / Encoder.RepairFlaggedDevice."""
     if len(expected) != nseg:
         raise ValueError("expected needs one dict per segment")
     which = [(s, i, bytes(h)) for s in range(nseg) for i, h in expected[s].items()]

@@ -265,6 +265,60 @@ int cec_reconstruct_partial_ptrs(cec_codec* codec, const uint8_t* const* src,
  *    enqueued on hip_stream and not waited for. */
 int cec_xor_ptrs(cec_codec* codec, uint8_t* const* dst, const uint8_t* const* src, size_t nrows,
                  size_t nsrc, size_t len, void* hip_stream);
+/* Heal flagged fragments: a rebuild whose "which shard is bad" comes from flags in DEVICE memory,
+ * such as cec_hashq_add_check_concat_ptrs and cec_verify_ptrs leave there, decided per segment on
+ * the GPU and done in place, on the stream that produced the flags, with no host round trip (the
+ * off-chain half of generate_restoral_order / restoral_order_complete,
+ * c-pallets/file-bank/src/lib.rs:943-1122, after a scrub). Per segment, one of: */
+#define CEC_FLAG_CLEAN 0   /* no held shard flagged bad: nothing written */
+#define CEC_FLAG_REBUILT 1 /* exactly one bad, >= k good: that shard rewritten in place */
+#define CEC_FLAG_MANY 2    /* two or more bad, >= k good: nothing written (host path can rebuild) */
+#define CEC_FLAG_LOST 3    /* at least one bad and fewer than k good: nothing written */
+/* Host only: the rule the device applies to one segment. held, flags: k+m bytes each. bad = held
+ * and flag == 0, good = held and flag != 0 (flags of shards not held are ignored). bad == 0:
+ * CEC_FLAG_CLEAN, whatever the held count. bad == 1 and good >= k: CEC_FLAG_REBUILT, and *lost
+ * (may be NULL) receives that shard's index; -1 for every other status. bad >= 2 and good >= k:
+ * CEC_FLAG_MANY. Anything else: CEC_FLAG_LOST. */
+int cec_flag_status(int k, int m, const uint8_t* held, const uint8_t* flags, int* status,
+                    int* lost);
+/* With n = k+m: shards is a HOST array of nseg*n DEVICE pointers laid out as in
+ * cec_reconstruct_ptrs, NULL = the shard is not held here. d_flags: DEVICE memory of nseg*n bytes
+ * at any alignment, d_flags[s*n+i] != 0 = held shard i of segment s is good, 0 = it is bad: the
+ * layout cec_hashq_add_check_concat_ptrs writes when its chains are listed segment-major. d_status:
+ * DEVICE memory of nseg bytes, receives one CEC_FLAG_* code per segment by the rule of
+ * cec_flag_status. The bad shard j of a CEC_FLAG_REBUILT segment is recomputed from the k
+ * survivors cec_survivors names for the pattern (held \ {j}) and written over the shard_len bytes
+ * at shards[s*n+j]. For RS(2,1) one bad fragment per segment is all the code can repair; for
+ * wider codes this is the single-failure case, and CEC_FLAG_MANY segments are reported untouched
+ * for cec_reconstruct_ptrs to take.
+ *  - Reads: d_flags (bytes of shards not held are not looked at), and for REBUILT segments only
+ *    those k survivors. No shard of any other segment is read.
+ *  - Writes: d_status, and the bad shard of each REBUILT segment. d_flags is not written.
+ *  - Not waited for: everything that depends on the flags is enqueued on hip_stream and the call
+ *    returns; the flags may still be in production by work queued earlier on that stream. The call
+ *    neither synchronises hip_stream nor copies any flag to the host. (It waits for the codec's
+ *    own upload stream, for its table, as the other _ptrs calls do.)
+ *  - Validation: everything is validated before anything is enqueued; on an error no byte is
+ *    written. CEC_EINVAL: a NULL codec; with nseg > 0 a NULL shards, d_flags or d_status; the same
+ *    non-NULL shard address twice anywhere in the call (any of them may become a destination;
+ *    equal addresses are what is checked, as in cec_xor_ptrs). CEC_ESHARDLEN: shard_len == 0.
+ *    nseg == 0: CEC_OK.
+ *  - Alignment: any alignment and any shard_len >= 1 is correct. When every held address is
+ *    16-byte aligned the kernels take vector columns with a byte tail, otherwise the whole call
+ *    runs byte-wise (the fallback is per call).
+ *  - Pointer array: it belongs to the caller again on return. The device tables (the addresses, the
+ *    candidate programs, the rows the planner kernel writes) come from the codec's pool and are
+ *    retired behind the launches: CEC_STAT_POOL_BYTES does not grow across repeated calls.
+ *  - HIP graph capture: not capturable, for the reasons given at cec_reconstruct_ptrs.
+ * Decode programs (every code but RS(2,1) without CEC_OPT_FORCE_GENERIC, whose closed forms need
+ * none): one per held set and held shard j, prepared before the flags are known, from the codec's
+ * LRU cache under the keys cec_reconstruct_ptrs uses for (held \ {j}, required {j}), so the two
+ * calls share entries; the call holds them until its launches are marked, so a cache capacity of
+ * 1 stays correct. A planner kernel applies the rule and writes one table row per segment; the
+ * table-addressed kernels then run over every row, and a segment that is not REBUILT costs one
+ * row of workgroups that leave after one scalar load. */
+int cec_repair_flagged_ptrs(cec_codec* codec, uint8_t* const* shards, const uint8_t* d_flags,
+                            size_t nseg, size_t shard_len, uint8_t* d_status, void* hip_stream);
 /* ---- parity accumulated shard by shard (klauspost EncodeIdx and Update) -----------------------
  * Both are one primitive on the codec's encode matrix E (cec_matrix; row k+o is parity shard o):
  *   parity[o] ^= E[k+o][j] * x_j   for every o < m,

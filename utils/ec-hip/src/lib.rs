@@ -185,6 +185,11 @@ pub mod sys {
         pub fn cec_xor_ptrs(c: *mut cec_codec, dst: *const *mut u8, src: *const *const u8,
                             nrows: usize, nsrc: usize, len: usize,
                             stream: *mut c_void) -> c_int;
+        pub fn cec_flag_status(k: c_int, m: c_int, held: *const u8, flags: *const u8,
+                               status: *mut c_int, lost: *mut c_int) -> c_int;
+        pub fn cec_repair_flagged_ptrs(c: *mut cec_codec, shards: *const *mut u8,
+                                       d_flags: *const u8, nseg: usize, shard_len: usize,
+                                       d_status: *mut u8, stream: *mut c_void) -> c_int;
         pub fn cec_encode_idx_batch(c: *mut cec_codec, d_shard: *const u8,
                                     shard_seg_stride: usize, idx: c_int, d_parity: *mut u8,
                                     nseg: usize, shard_len: usize, accumulate: c_int,
@@ -395,6 +400,10 @@ pub const CEC_EINVAL: c_int = -1;
 pub const CEC_ETOOFEW: c_int = -2;
 pub const CEC_ESHARDLEN: c_int = -3;
 pub const CEC_ESEGCOUNT: c_int = -9;
+pub const CEC_FLAG_CLEAN: c_int = 0;
+pub const CEC_FLAG_REBUILT: c_int = 1;
+pub const CEC_FLAG_MANY: c_int = 2;
+pub const CEC_FLAG_LOST: c_int = 3;
 pub const SEGMENT_COUNT: usize = 1000; // runtime/src/lib.rs:1026
 pub const FRAGMENT_COUNT: usize = 3; // runtime/src/lib.rs:1027
 
@@ -638,6 +647,47 @@ impl ReedSolomon {
             return Err(Error::from_code(CEC_EINVAL));
         }
         check(cec_xor_ptrs(self.c, dst.as_ptr(), src.as_ptr(), dst.len(), nsrc, len, stream))
+    }
+
+    /// Heal flagged fragments in place (`cec_repair_flagged_ptrs`): `shards` holds `nseg * (k + m)`
+    /// device addresses, segment by segment, null = not held. `d_flags` (device, one byte per
+    /// entry of `shards`, 0 = that held shard is bad; what `hashq_add_check_concat_ptrs` writes for
+    /// chains listed segment-major) is read on the GPU: a segment with exactly one bad shard and at
+    /// least k good ones has that shard rebuilt over its address. `d_status` (device, `nseg` bytes)
+    /// receives one `CEC_FLAG_*` code per segment (`flag_status` states the rule). Enqueued on
+    /// `stream` and not waited for, and no flag is copied to the host: the flags may still be in
+    /// production by work queued earlier on that stream. The slice may be reused as soon as the
+    /// call returns.
+    ///
+    /// # Safety
+    /// Every non-null address must be device memory of `shard_len` bytes on the codec's GPU
+    /// (`d_flags`: one byte per entry, `d_status`: `nseg` bytes) that stays valid until the stream
+    /// has passed the call's work; shards must not overlap each other.
+    pub unsafe fn repair_flagged_ptrs(&self, shards: &[*mut u8], d_flags: *const u8,
+                                      shard_len: usize, d_status: *mut u8,
+                                      stream: *mut c_void) -> Result<(), Error> {
+        let n = self.k + self.m;
+        if shards.len() % n != 0 {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        check(cec_repair_flagged_ptrs(self.c, shards.as_ptr(), d_flags, shards.len() / n,
+                                      shard_len, d_status, stream))
+    }
+
+    /// The rule `repair_flagged_ptrs` applies to one segment (`cec_flag_status`, host only):
+    /// `held` and `flags` hold k + m bytes each. Returns the `CEC_FLAG_*` status and, for
+    /// `CEC_FLAG_REBUILT`, the index of the shard that is rewritten.
+    pub fn flag_status(&self, held: &[u8], flags: &[u8]) -> Result<(i32, Option<usize>), Error> {
+        let n = self.k + self.m;
+        if held.len() != n || flags.len() != n {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        let (mut status, mut lost): (c_int, c_int) = (0, -1);
+        check(unsafe {
+            cec_flag_status(self.k as c_int, self.m as c_int, held.as_ptr(), flags.as_ptr(),
+                            &mut status, &mut lost)
+        })?;
+        Ok((status, if lost >= 0 { Some(lost as usize) } else { None }))
     }
 
     /// EncodeIdx on scattered device shards in place (`cec_encode_idx_ptrs`): `data` holds
