@@ -5,7 +5,13 @@ this package is the host-side mirror of the off-chain codec API (klauspost/reeds
 plus the CESS segment / fragment records.
 """
 from . import audit, geometry, records
-from ._lib import CEC_FLAG_CLEAN, CEC_FLAG_LOST, CEC_FLAG_MANY, CEC_FLAG_REBUILT
+from ._lib import (
+    CEC_FLAG_CLEAN,
+    CEC_FLAG_LOST,
+    CEC_FLAG_MANY,
+    CEC_FLAG_MULTI_MAX,
+    CEC_FLAG_REBUILT,
+)
 from .hashq import HashQueue, sha256_blocks
 from .records import ErrTooManySegments
 from .reedsolomon import (
@@ -24,6 +30,7 @@ from .reedsolomon import (
     decode_rows,
     fill_synthetic,
     flag_status,
+    flag_status_multi,
     sha256_hex_device,
     sha256_hex_host,
     xor_batch,
@@ -35,5 +42,5 @@ __all__ = [
     "ErrTooFewShards", "HipError", "fill_synthetic", "sha256_hex_device", "sha256_hex_host",
     "HashQueue", "sha256_blocks", "records", "ErrTooManySegments", "audit", "xor_batch",
     "ErrInvalidInput", "decode_rows", "flag_status", "CEC_FLAG_CLEAN", "CEC_FLAG_REBUILT",
-    "CEC_FLAG_MANY", "CEC_FLAG_LOST",
+    "CEC_FLAG_MANY", "CEC_FLAG_LOST", "CEC_FLAG_MULTI_MAX", "flag_status_multi",
 ]

@@ -88,6 +88,13 @@ SIGNATURES = {
                                 POINTER(c_int), POINTER(c_int)]),
     "cec_repair_flagged_ptrs": (c_int, [c_void_p, POINTER(c_void_p), c_void_p, c_size_t,
                                         c_size_t, c_void_p, c_void_p]),
+    "cec_flag_status_multi": (c_int, [c_int, c_int, POINTER(c_uint8), POINTER(c_uint8), c_int,
+                                      POINTER(c_int), POINTER(c_int), POINTER(c_uint8)]),
+    "cec_flag_solve": (c_int, [c_int, c_int, POINTER(c_uint8), POINTER(c_uint8), c_int,
+                               POINTER(c_int), POINTER(c_int), POINTER(c_uint8), POINTER(c_uint8),
+                               POINTER(c_uint8)]),
+    "cec_repair_flagged_multi_ptrs": (c_int, [c_void_p, POINTER(c_void_p), c_void_p, c_size_t,
+                                              c_size_t, c_int, c_void_p, c_void_p]),
     "cec_encode_idx_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_size_t,
                                      c_size_t, c_int, c_void_p]),
     "cec_update_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,
@@ -231,6 +238,7 @@ CEC_FLAG_CLEAN = 0
 CEC_FLAG_REBUILT = 1
 CEC_FLAG_MANY = 2
 CEC_FLAG_LOST = 3
+CEC_FLAG_MULTI_MAX = 4
 CEC_HQOPT_TICK = 1
 CEC_PIPE_HASH_NONE = 0
 CEC_PIPE_HASH_GPU = 1

@@ -146,6 +146,23 @@ def scrub_repair_device(enc: Encoder, segments: Sequence, recorded, queue=None):
     not re-checked: a caller who wants proof scrubs again (a fragment whose *record* is wrong is
     rebuilt to the same bytes and flagged again). queue None: a queue of the call's size on
     torch's current stream, owned and closed by the call, as in scrub_device."""
+    return _scrub_repair(enc, segments, recorded, queue, enc.RepairFlaggedDevice)
+
+
+def scrub_repair_multi_device(enc: Encoder, segments: Sequence, recorded,
+                              max_bad: int = _lib.CEC_FLAG_MULTI_MAX, queue=None):
+    """scrub_repair_device for the wider codes, where several fragments of a segment may be gone
+    at once: the same checked chains and ticks, then Encoder.RepairFlaggedMultiDevice reads the
+    flags: a segment with 1 to `max_bad` fragments that no longer hash to their records, and at
+    least k that do, has all of them rebuilt in place. Arguments and the returned (d_flags,
+    d_status) as there."""
+    def repair(segs, d_flags, stream):
+        return enc.RepairFlaggedMultiDevice(segs, d_flags, max_bad=max_bad, stream=stream)
+    return _scrub_repair(enc, segments, recorded, queue, repair)
+
+
+def _scrub_repair(enc, segments, recorded, queue, repair):
+    """The scrub of the two calls above; repair(segments, d_flags, stream=...) ends it."""
     import torch
     from .hashq import HashQueue
     segments = [list(seg) for seg in segments]
@@ -181,7 +198,7 @@ def scrub_repair_device(enc: Encoder, segments: Sequence, recorded, queue=None):
             q.add_check_ptrs(slots[a:b], rec[a:b], flat[a:b])
         q.finish()
         stream = q.stream if q.stream is not None else 0  # a queue without one: the null stream
-        return enc.RepairFlaggedDevice(segments, d_flags, stream=stream)
+        return repair(segments, d_flags, stream=stream)
 
     if queue is not None:
         return d_flags, go(queue)

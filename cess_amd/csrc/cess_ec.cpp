@@ -31,6 +31,7 @@
 #include "../../include/cess_ec.h"
 #include "fftdec_cost.h"
 #include "fftdec_plan.h"
+#include "flag_solve.h"
 #include "gf256.h"
 #include "host_util.h"
 #include "kernels.h"
@@ -1954,7 +1955,7 @@ static int repair_flagged_impl(cec_codec* c, uint8_t* const* shards, const uint8
     cec::launch_ptrs_rs21(cec::PtrSink::store, fp.rows, fp.nseg, shard_len, vec_ok, nullptr, st);
     rc = check_launch();
   } else if (!rc && any_prog) {  // without a program every row is idle
-    cec::launch_ptrs_rt_flag(cec::rt_takes_rtb(c->opts, 1, k), fp.rows, fp.nseg, rs, shard_len,
+    cec::launch_ptrs_rt_flag(cec::rt_takes_rtb(c->opts, 1, k), fp.rows, fp.nseg, rs, 1, shard_len,
                              vec_ok, st);
     rc = check_launch();
   }
@@ -1972,6 +1973,134 @@ int cec_repair_flagged_ptrs(cec_codec* c, uint8_t* const* shards, const uint8_t*
   CEC_HIP_TRY(hipSetDevice(c->device));
   return repair_flagged_impl(c, shards, d_flags, nseg, shard_len, d_status,
                              pick_stream(c, hip_stream));
+}
+
+static_assert(CEC_FLAG_MULTI_MAX == cec::kFlagMultiMax, "the planner kernel's bound");
+static_assert(CEC_FLAG_CLEAN == cec::kFsClean && CEC_FLAG_REBUILT == cec::kFsRebuilt &&
+                  CEC_FLAG_MANY == cec::kFsMany && CEC_FLAG_LOST == cec::kFsLost,
+              "flag_solve.h states the rule in the header's codes");
+
+static int check_flag_multi(int k, int m, int max_bad) {
+  if (k < 1 || m < 1 || k + m > cec::kMaxShards)
+    return set_err(CEC_EINVAL, "need k >= 1, m >= 1, k + m <= 256");
+  if (max_bad < 1 || max_bad > CEC_FLAG_MULTI_MAX)
+    return set_err(CEC_EINVAL, "max_bad must be 1..CEC_FLAG_MULTI_MAX");
+  return CEC_OK;
+}
+
+int cec_flag_solve(int k, int m, const uint8_t* held, const uint8_t* flags, int max_bad,
+                   int* status, int* nout, uint8_t* out_idx, uint8_t* in_idx, uint8_t* rows) {
+  if (!held || !flags || !status || !nout) return set_err(CEC_EINVAL, "null");
+  if (int rc = check_flag_multi(k, m, max_bad)) return rc;
+  uint32_t st = 0, e = 0;
+  cec::fs_plan_segment((uint32_t)k, (uint32_t)(k + m), held, flags, (uint32_t)max_bad, &st, &e,
+                       out_idx, in_idx, rows, nullptr);
+  *status = (int)st;
+  *nout = (int)e;
+  return CEC_OK;
+}
+
+int cec_flag_status_multi(int k, int m, const uint8_t* held, const uint8_t* flags, int max_bad,
+                          int* status, int* nlost, uint8_t* lost) {
+  if (!nlost) return set_err(CEC_EINVAL, "null");
+  return cec_flag_solve(k, m, held, flags, max_bad, status, nlost, lost, nullptr, nullptr);
+}
+
+// cec_repair_flagged_multi_ptrs: nothing about a segment is known on the host but what it holds,
+// so the host uploads the addresses and nothing else; the planner kernel (kernels.h
+// FlagPlanMulti) solves every rebuilt segment's rows and writes its program chunk and its table
+// row. One table per bucket b <= max_bad that some held set of the call can fill (k + b shards
+// held), one product launch over all of it behind the planner. Nothing here waits for `st` or
+// copies from the device, and the decode cache is not touched.
+static int repair_flagged_multi_impl(cec_codec* c, uint8_t* const* shards, const uint8_t* d_flags,
+                                     size_t nseg, size_t shard_len, int max_bad,
+                                     uint8_t* d_status, hipStream_t st) {
+  const int n = c->k + c->m, k = c->k;
+  std::unordered_set<uintptr_t> seen;
+  uintptr_t bits = 0;  // OR of every held address: the alignment of the call
+  std::vector<uint64_t> host(nseg * n, 0);
+  int most = 0;  // the largest held set
+  for (size_t s = 0; s < nseg; ++s) {
+    int nheld = 0;
+    for (int i = 0; i < n; ++i) {
+      uint8_t* const a = shards[s * n + i];
+      if (!a) continue;
+      if (!seen.insert((uintptr_t)a).second)
+        return set_err(CEC_EINVAL, "a shard address is named twice");
+      bits |= (uintptr_t)a;
+      host[s * n + i] = (uint64_t)(uintptr_t)a;
+      ++nheld;
+    }
+    most = std::max(most, nheld);
+  }
+  const bool vec_ok = (bits & 15) == 0;
+  const int widest = std::min({max_bad, c->m, most - k});  // < 1: every row of the call is idle
+  // one pool block: the addresses, then bucket b's table [nseg][k + 1 + b]
+  size_t words = host.size(), rows_at[CEC_FLAG_MULTI_MAX] = {};
+  for (int b = 1; b <= widest; ++b) {
+    rows_at[b - 1] = words;
+    words += nseg * (size_t)(k + 1 + b);
+  }
+  const size_t bytes = words * sizeof(uint64_t);
+  void* d = nullptr;
+  int rc = c->pool.alloc(bytes, &d);
+  if (rc) return rc;
+  // the segments' chunks: written and read on `st` only, so a large block is stream-ordered
+  const size_t chunk_words = widest < 1 ? 0 : cec::fs_chunk_words((uint32_t)k, (uint32_t)widest);
+  Scratch progs;
+  if (chunk_words) rc = scratch_alloc(c, nseg * chunk_words * sizeof(uint32_t), st, &progs);
+  hipError_t e = hipSuccess;
+  if (!rc) {
+    e = hipMemcpyAsync(d, host.data(), host.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
+                       c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess)
+      rc = set_err(CEC_EHIP, std::string("table upload: ") + hipGetErrorString(e));
+  }
+  if (rc) {
+    c->pool.retire(d, bytes);
+    scratch_release(c, progs, st);
+    return rc;
+  }
+  uint64_t* dw = static_cast<uint64_t*>(d);
+  cec::FlagPlanMulti fp{};
+  fp.segs = dw;
+  fp.flags = d_flags;
+  fp.status = d_status;
+  for (int b = 1; b <= widest; ++b) fp.rows[b - 1] = dw + rows_at[b - 1];
+  fp.chunks = static_cast<uint32_t*>(progs.p);
+  fp.chunk_words = (uint32_t)chunk_words;
+  fp.nseg = (uint32_t)nseg;
+  fp.n = n;
+  fp.k = k;
+  fp.max_bad = max_bad;
+  cec::launch_flag_plan_multi(fp, st);
+  rc = check_launch();
+  for (int b = 1; b <= widest && !rc; ++b) {
+    cec::launch_ptrs_rt_flag(cec::rt_takes_rtb(c->opts, b, k), fp.rows[b - 1], fp.nseg,
+                             (uint32_t)(k + 1 + b), b, shard_len, vec_ok, st);
+    rc = check_launch();
+  }
+  const int mrc = c->pool.mark(st);  // the tables and the chunks stay until these complete
+  c->pool.retire(d, bytes);
+  scratch_release(c, progs, st);
+  return rc ? rc : mrc;
+}
+
+int cec_repair_flagged_multi_ptrs(cec_codec* c, uint8_t* const* shards, const uint8_t* d_flags,
+                                  size_t nseg, size_t shard_len, int max_bad, uint8_t* d_status,
+                                  void* hip_stream) {
+  if (!c || (nseg && (!shards || !d_flags || !d_status))) return set_err(CEC_EINVAL, "null");
+  if (int rc = check_flag_multi(c->k, c->m, max_bad)) return rc;
+  if (int rc = check_batch(nseg, shard_len)) return rc;
+  if (nseg == 0) return CEC_OK;
+  CEC_HIP_TRY(hipSetDevice(c->device));
+  // one bad shard per segment at the most: the single-failure call, its planners and products
+  if (c->m == 1 || max_bad == 1)
+    return repair_flagged_impl(c, shards, d_flags, nseg, shard_len, d_status,
+                               pick_stream(c, hip_stream));
+  return repair_flagged_multi_impl(c, shards, d_flags, nseg, shard_len, max_bad, d_status,
+                                   pick_stream(c, hip_stream));
 }
 
 int cec_reconstruct_partial_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size_t nseg,

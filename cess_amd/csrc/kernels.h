@@ -181,10 +181,32 @@ struct FlagPlan {
 // segment). Otherwise rows {program chunk, k inputs, 1 output}, k + 2 words, for
 // launch_ptrs_rt_flag, a segment that is not rebuilt gets an all-zero row (one wave per segment).
 void launch_flag_plan(const FlagPlan& p, bool rs21, hipStream_t st);
-// launch_ptrs_rt's store form for one-output chunks (nob == 1) over rows a planner wrote: a row
-// whose word 0 is zero is left before its program chunk or any of its addresses is looked at.
-void launch_ptrs_rt_flag(bool bitplane, const uint64_t* tab, uint32_t nrows, uint32_t rs,
+// launch_ptrs_rt's store form for chunks of a bucket nob in 1..4 (nothing is launched for another)
+// over rows a planner wrote: a row whose word 0 is zero is left before its program chunk or any
+// of its addresses is looked at.
+void launch_ptrs_rt_flag(bool bitplane, const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob,
                          uint64_t len, bool vec_ok, hipStream_t st);
+
+// Several bad shards per segment (cec_repair_flagged_multi_ptrs): the planner also solves the
+// decode rows, per segment, from the flags (flag_solve.h: the Lagrange form, no inversion), so the
+// host prepares no program. The rule is cec_flag_status_multi's: up to max_bad (<= kFlagMultiMax)
+// bad shards and >= k good ones: rebuilt, all of them, from the first k good shards in index order.
+struct FlagPlanMulti {
+  const uint64_t* segs;   // [nseg][n]: a segment's n shard addresses (0: not held)
+  const uint8_t* flags;   // [nseg][n], any alignment; bytes of shards not held are not read
+  uint8_t* status;        // [nseg]: kFlag* per segment
+  uint64_t* rows[4];      // rows[b - 1]: the table of bucket b, [nseg][k + 1 + b] words; null: no
+                          // segment of the call can have b bad shards rebuilt, no table
+  uint32_t* chunks;       // [nseg][chunk_words]: segment s's program chunk (flag_solve.h)
+  uint32_t chunk_words;   // fs_chunk_words(k, the widest bucket with a table)
+  uint32_t nseg;
+  int n, k, max_bad;
+};
+// One wave per segment. A segment rebuilt with e bad shards gets the row {its chunk, the addresses
+// of its first k good shards, of its e bad ones} in bucket e's table and its chunk written (header
+// {k, e, e, 0}, hb, masks); in every other table its row is idle: word 0 zero, the rest unwritten.
+// Row s and chunk s are segment s's: no atomics, no compaction, the tables of two runs are equal.
+void launch_flag_plan_multi(const FlagPlanMulti& p, hipStream_t st);
 
 // SHA-256 of `n` equal-length buffers, written as 64 lowercase hex characters each into
 // `hex_out` (device, n * 64 bytes). If `ptrs` is null, buffer i is shard (i % nshards) of

@@ -22,6 +22,7 @@
 #include <utility>
 
 #include "dev_util.h"
+#include "flag_solve.h"
 #include "gf256.h"
 #include "kernels.h"
 
@@ -1996,6 +1997,78 @@ __global__ __launch_bounds__(256) void k_flag_plan(FlagPlan p) {
   }
 }
 
+// Several bad shards per segment (kernels.h FlagPlanMulti): the wave of a segment also solves its
+// decode rows (flag_solve.h) and writes its program chunk. The lanes stride over the n flags; the
+// ballots give the counts, the first k good indices (in LDS, 256 bytes per wave, written and read
+// by this wave only) and the first four bad ones (wave-uniform, a byte each of one word). Then the
+// lanes stride over the k survivors: lane t writes survivor t's address into the row and input
+// column t into the chunk. N_j is computed by every lane for itself.
+static_assert(kFsHeaderWords == kRtHeaderWords, "flag_solve.h writes the chunk layout of kernels.h");
+static_assert(kFlagMultiMax == 4, "one table per bucket of the bit-plane product");
+static_assert(kFsClean == kFlagClean && kFsRebuilt == kFlagRebuilt && kFsMany == kFlagMany &&
+                  kFsLost == kFlagLost,
+              "one set of status codes");
+__global__ __launch_bounds__(256) void k_flag_plan_multi(FlagPlanMulti p) {
+  __shared__ uint8_t surv_all[4][256];
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t s = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= p.nseg) return;  // the whole wave
+  uint8_t* surv = surv_all[threadIdx.x >> 6];
+  const uint32_t n = (uint32_t)p.n, k = (uint32_t)p.k;
+  const uint64_t* __restrict__ seg = p.segs + s * n;
+  const uint8_t* __restrict__ fl = p.flags + s * n;
+  uint32_t nbad = 0, ngood = 0, lost = 0;
+  for (uint32_t base = 0; base < n; base += 64) {
+    const uint32_t i = base + lane;
+    const bool held = i < n && seg[i] != 0;
+    const bool good = held && fl[i] != 0;
+    unsigned long long bad = __ballot(held && !good);
+    const unsigned long long gm = __ballot(good);
+    const uint32_t pos = ngood + (uint32_t)__popcll(gm & ((1ull << lane) - 1));
+    if (good && pos < k) surv[pos] = (uint8_t)i;
+    ngood += (uint32_t)__popcll(gm);
+    for (; bad; bad &= bad - 1) {
+      if (nbad < 4) lost |= (base + (uint32_t)__ffsll(bad) - 1) << (8 * nbad);
+      ++nbad;
+    }
+  }
+  const uint32_t st = fs_status(nbad, ngood, k, (uint32_t)p.max_bad);
+  const uint32_t e = st == kFlagRebuilt ? nbad : 0;
+  uint64_t* row = nullptr;  // the segment's row in bucket e's table
+  if (lane == 0) p.status[s] = (uint8_t)st;
+#pragma unroll
+  for (uint32_t b = 1; b <= 4; ++b) {
+    uint64_t* const rb = p.rows[b - 1] ? p.rows[b - 1] + s * (k + 1 + b) : nullptr;
+    if (b == e) row = rb;
+    else if (rb && lane == 0) rb[0] = 0;
+  }
+  if (!row) return;  // no rebuild (a rebuilt segment's bucket always has a table)
+  // the survivor list is complete: LDS accesses of one wave complete in order
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  uint32_t* __restrict__ chunk = p.chunks + s * p.chunk_words;
+  uint32_t nj[4];
+#pragma unroll
+  for (uint32_t o = 0; o < 4; ++o) nj[o] = o < e ? fs_numer(surv, k, (lost >> (8 * o)) & 0xFFu) : 0;
+  if (lane == 0) {
+    fs_put_header(chunk, k, e);
+    row[0] = (uint64_t)(uintptr_t)chunk;
+#pragma unroll
+    for (uint32_t o = 0; o < 4; ++o)
+      if (o < e) row[1 + k + o] = seg[(lost >> (8 * o)) & 0xFFu];
+  }
+  for (uint32_t t = lane; t < k; t += 64) {
+    const uint32_t sv = surv[t];
+    row[1 + t] = seg[sv];
+    const uint32_t dt = fs_denom(surv, k, t);
+    uint32_t col = 0;
+#pragma unroll
+    for (uint32_t o = 0; o < 4; ++o)
+      if (o < e) col |= fs_coef(nj[o], (lost >> (8 * o)) & 0xFFu, sv, dt) << (8 * o);
+    fs_put_column(chunk, e, t, col);
+  }
+}
+
 namespace {
 // A launch's sink as a type: f(SinkTag<Sink>, the sink's kernel arguments...).
 template <class Sink>
@@ -2044,20 +2117,20 @@ void launch_ptrs_rt(PtrSink sink, bool bitplane, const uint64_t* tab, uint32_t n
   });
 }
 
-void launch_ptrs_rt_flag(bool bitplane, const uint64_t* tab, uint32_t nrows, uint32_t rs,
+void launch_ptrs_rt_flag(bool bitplane, const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob,
                          uint64_t len, bool vec_ok, hipStream_t st) {
   const int v = vec_ok ? 1 : 0;
-  // the one-output bucket's shapes, as launch_ptrs_rt picks them
+  if (nob < 1 || nob > 4) return;
+  // the bucket's shapes, as launch_ptrs_rt picks them
   if (bitplane) {
-    rtb_dispatch(1, [&]<int NOB, class TV, int PF>(RtbShape<NOB, TV, PF>) {
-      if constexpr (NOB == 1)
-        launch_rows(k_ptrb_flag<NOB, TV, PF>, rt_grid_x(len, sizeof(TV), 1, vec_ok), tab, nrows, st,
-                    rs, len, v);
+    rtb_dispatch(nob, [&]<int NOB, class TV, int PF>(RtbShape<NOB, TV, PF>) {
+      launch_rows(k_ptrb_flag<NOB, TV, PF>, rt_grid_x(len, sizeof(TV), 1, vec_ok), tab, nrows, st,
+                  rs, len, v);
     });
     return;
   }
-  rt_dispatch(1, [&]<int NOB, int U, class TV>(RtShape<NOB, U, TV>) {
-    if constexpr (NOB == 1)
+  rt_dispatch(nob, [&]<int NOB, int U, class TV>(RtShape<NOB, U, TV>) {
+    if constexpr (NOB <= 4)
       launch_rows(k_ptrt_flag<NOB, U, TV>, rt_grid_x(len, sizeof(TV), U, vec_ok), tab, nrows, st,
                   rs, len, v);
   });
@@ -2071,6 +2144,12 @@ void launch_flag_plan(const FlagPlan& p, bool rs21, hipStream_t st) {
   else
     hipLaunchKernelGGL(k_flag_plan, dim3((unsigned)(((uint64_t)p.nseg + 3) / 4)), dim3(256), 0,
                        st, p);
+}
+
+void launch_flag_plan_multi(const FlagPlanMulti& p, hipStream_t st) {
+  if (p.nseg == 0) return;
+  hipLaunchKernelGGL(k_flag_plan_multi, dim3((unsigned)(((uint64_t)p.nseg + 3) / 4)), dim3(256), 0,
+                     st, p);
 }
 
 }  // namespace cec

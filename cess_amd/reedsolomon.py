@@ -485,6 +485,27 @@ class Encoder:
         without parity shards, which can heal nothing). Enqueued on `stream`
         (default: torch's current stream) and not waited for, and no flag is copied to the host:
         the flags may still be in production by work queued earlier on that stream."""
+        return self._repair_flagged(segments, d_flags, d_status, stream, None,
+                                    "RepairFlaggedDevice")
+
+    def RepairFlaggedMultiDevice(self, segments: Sequence, d_flags,
+                                 max_bad: int = _lib.CEC_FLAG_MULTI_MAX, d_status=None,
+                                 stream=None):
+        """RepairFlaggedDevice for segments with several bad shards
+        (cec_repair_flagged_multi_ptrs): a segment with 1 to `max_bad` bad shards (at most
+        CEC_FLAG_MULTI_MAX) and at least k good ones gets every bad shard rebuilt over its tensor,
+        from the first k good shards in index order; the decode rows are solved per segment on the
+        GPU, so nothing is prepared for the patterns on the host. Arguments, checks, stream
+        behaviour and the returned status tensor are RepairFlaggedDevice's (flag_status_multi
+        states the rule); `max_bad` outside 1..CEC_FLAG_MULTI_MAX raises ErrInvalidInput. With
+        max_bad == 1, or one parity shard, it is RepairFlaggedDevice."""
+        if not 1 <= int(max_bad) <= _lib.CEC_FLAG_MULTI_MAX:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        return self._repair_flagged(segments, d_flags, d_status, stream, int(max_bad),
+                                    "RepairFlaggedMultiDevice")
+
+    def _repair_flagged(self, segments, d_flags, d_status, stream, max_bad, what):
+        """The two forms above: max_bad None is cec_repair_flagged_ptrs."""
         import torch
         nseg, n = len(segments), self.Shards
         dev = torch.device("cuda", self.device)
@@ -511,9 +532,15 @@ class Encoder:
                 held.append(_on_gpu(t, dev))
                 ptrs[s * n + i] = _dev_ptr(t)
         size = self._check_device_shards(held)
-        check(self._lib.cec_repair_flagged_ptrs(self._h, ptrs, _dev_ptr(d_flags), nseg, size,
-                                                _dev_ptr(d_status), self._device_stream(stream)),
-              "RepairFlaggedDevice")
+        if max_bad is None:
+            rc = self._lib.cec_repair_flagged_ptrs(self._h, ptrs, _dev_ptr(d_flags), nseg, size,
+                                                   _dev_ptr(d_status),
+                                                   self._device_stream(stream))
+        else:
+            rc = self._lib.cec_repair_flagged_multi_ptrs(self._h, ptrs, _dev_ptr(d_flags), nseg,
+                                                         size, max_bad, _dev_ptr(d_status),
+                                                         self._device_stream(stream))
+        check(rc, what)
         return d_status
 
     def ReconstructPartialDevice(self, shards: Sequence, present, out=None,
@@ -916,6 +943,25 @@ def flag_status(data_shards: int, parity_shards: int, held, flags):
                                       f.ctypes.data_as(u8p), byref(status), byref(lost)),
           "flag_status")
     return status.value, lost.value
+
+
+def flag_status_multi(data_shards: int, parity_shards: int, held, flags, max_bad: int):
+    """Host only (cec_flag_status_multi): the rule RepairFlaggedMultiDevice applies to one segment
+    on the GPU. `held` and `flags` are k+m values each (a held shard whose flag is 0 is bad).
+    Returns (CEC_FLAG_* status, the ascending list of the shards a REBUILT segment rewrites, empty
+    for every other status)."""
+    n = data_shards + parity_shards
+    h = np.ascontiguousarray(np.asarray(held, dtype=np.uint8))
+    f = np.ascontiguousarray(np.asarray(flags, dtype=np.uint8))
+    if h.shape != (n,) or f.shape != (n,):
+        raise ValueError("held and flags must have k+m values")
+    status, nlost = c_int(-1), c_int(0)
+    lost = (c_uint8 * _lib.CEC_FLAG_MULTI_MAX)()
+    u8p = POINTER(c_uint8)
+    check(_lib.load().cec_flag_status_multi(data_shards, parity_shards, h.ctypes.data_as(u8p),
+                                            f.ctypes.data_as(u8p), max_bad, byref(status),
+                                            byref(nlost), lost), "flag_status_multi")
+    return status.value, [int(x) for x in lost[:nlost.value]]
 
 
 def fill_synthetic(d_out, seg_bytes: int, nseg: int, seg0: int, seed: int, stream=None) -> None:

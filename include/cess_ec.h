@@ -319,6 +319,67 @@ int cec_flag_status(int k, int m, const uint8_t* held, const uint8_t* flags, int
  * row of workgroups that leave after one scalar load. */
 int cec_repair_flagged_ptrs(cec_codec* codec, uint8_t* const* shards, const uint8_t* d_flags,
                             size_t nseg, size_t shard_len, uint8_t* d_status, void* hip_stream);
+/* Several bad shards per segment: the same heal for the wider codes, where a miner exit takes
+ * several fragments of a segment at once. Up to max_bad bad shards of a segment are rebuilt, the
+ * decode rows solved on the GPU from the flags. The cap: */
+#define CEC_FLAG_MULTI_MAX 4 /* the bit-plane product exists for one to four outputs */
+/* Host only: the rule with a bound. bad and good as in cec_flag_status. bad == 0: CEC_FLAG_CLEAN.
+ * good < k: CEC_FLAG_LOST. bad <= max_bad: CEC_FLAG_REBUILT, every bad shard is rewritten; *nlost
+ * receives their count and lost[0 .. *nlost) (CEC_FLAG_MULTI_MAX bytes, may be NULL) their indices,
+ * ascending. Otherwise CEC_FLAG_MANY. *nlost is 0 and lost is not written for every status but
+ * REBUILT. No status value is added. max_bad must be in [1, CEC_FLAG_MULTI_MAX] (CEC_EINVAL); with
+ * max_bad == 1 the rule is cec_flag_status's. */
+int cec_flag_status_multi(int k, int m, const uint8_t* held, const uint8_t* flags, int max_bad,
+                          int* status, int* nlost, uint8_t* lost);
+/* Host only: what the device computes for one segment. Status and *nout as above; for a REBUILT
+ * segment out_idx[0 .. *nout) (CEC_FLAG_MULTI_MAX bytes) are the bad shards, ascending, in_idx[0 .. k)
+ * the survivors read, the first k good shards in index order, and rows (CEC_FLAG_MULTI_MAX * k
+ * bytes) the decode rows: out_idx[o] = XOR_t rows[o*k + t] * in_idx[t] over GF(2^8). out_idx,
+ * in_idx and rows may each be NULL. This codec's shard r is f(r) for one polynomial f of degree
+ * < k (the Vandermonde convention of cec_matrix), so a row is the Lagrange basis over the
+ * survivors, rows[o*k + t] = prod_{u != t} (j ^ S_u) / prod_{u != t} (S_t ^ S_u) with j =
+ * out_idx[o], S = in_idx: no matrix is inverted, and no coefficient is zero. The function runs the
+ * planner kernel's own arithmetic (csrc/flag_solve.h) with loops in place of lanes. */
+int cec_flag_solve(int k, int m, const uint8_t* held, const uint8_t* flags, int max_bad,
+                   int* status, int* nout, uint8_t* out_idx, uint8_t* in_idx, uint8_t* rows);
+/* cec_repair_flagged_ptrs with the rule of cec_flag_status_multi: shards, d_flags, d_status, nseg
+ * and shard_len as there; every bad shard of a CEC_FLAG_REBUILT segment is recomputed and written
+ * over the shard_len bytes at its address. Everything cec_repair_flagged_ptrs promises holds here:
+ *  - Reads: d_flags (bytes of shards not held are not looked at), and for REBUILT segments only
+ *    their survivors. No shard of any other segment is read. Writes: d_status, and the bad shards
+ *    of each REBUILT segment; d_flags is not written and nothing of a segment that is not REBUILT
+ *    is touched.
+ *  - Survivors: the first k good shards in index order, for every code, RS(32,32) included (the
+ *    survivor set cec_survivors prefers for RS(32,32) serves the FFT-domain decoders, which this
+ *    call never runs; any k survivors give the same bytes). Held shards flagged good past the
+ *    first k are not read.
+ *  - Not waited for: neither synchronises hip_stream nor copies any flag to the host; the flags
+ *    may still be in production by work queued earlier on that stream.
+ *  - Validation: before anything is enqueued; on an error no byte is written. CEC_EINVAL: a NULL
+ *    codec; max_bad outside [1, CEC_FLAG_MULTI_MAX]; with nseg > 0 a NULL shards, d_flags or
+ *    d_status; the same non-NULL shard address twice anywhere in the call. CEC_ESHARDLEN:
+ *    shard_len == 0. nseg == 0: CEC_OK.
+ *  - Alignment: any; 16-byte columns when every held address is 16-byte aligned, otherwise the
+ *    whole call runs byte-wise.
+ *  - The device tables come from the codec's pool and are retired behind the launches
+ *    (CEC_STAT_POOL_BYTES does not grow across repeated calls). Not capturable.
+ * What differs: the decode rows are solved on the device, per segment, so no decode program is
+ * prepared on the host and the LRU cache is neither read nor filled (CEC_STAT_DECODE_CACHED does
+ * not change). The host uploads the nseg*n addresses and nothing else. A planner kernel (one wave
+ * per segment) applies the rule, solves the rows and writes the segment's program chunk and its
+ * row in the table of its bucket b = the count of its bad shards; then one launch of the
+ * table-addressed product per bucket b <= min(max_bad, m) for which some held set of the call
+ * holds k+b shards, each over all nseg rows, where a segment of another bucket costs one row of
+ * workgroups that leave after one scalar load. Device footprint per segment, with e the widest
+ * such bucket: 8n bytes of addresses, 8(k+1+b) per bucket b <= e of table rows and 4(772 + 8ke)
+ * of program chunk; for RS(32,32) at max_bad 4 that is 512 + 1136 + 7184 bytes. The chunks are one
+ * block, a pool block below 16 MiB and stream-ordered scratch on hip_stream from there on.
+ * With m == 1 or max_bad == 1 the call is cec_repair_flagged_ptrs itself: same planners, same
+ * products, same bytes. Not covered: more than CEC_FLAG_MULTI_MAX bad shards per segment
+ * (CEC_FLAG_MANY, for cec_reconstruct_ptrs to take). */
+int cec_repair_flagged_multi_ptrs(cec_codec* codec, uint8_t* const* shards, const uint8_t* d_flags,
+                                  size_t nseg, size_t shard_len, int max_bad, uint8_t* d_status,
+                                  void* hip_stream);
 /* ---- parity accumulated shard by shard (klauspost EncodeIdx and Update) -----------------------
  * Both are one primitive on the codec's encode matrix E (cec_matrix; row k+o is parity shard o):
  *   parity[o] ^= E[k+o][j] * x_j   for every o < m,

@@ -190,6 +190,16 @@ pub mod sys {
         pub fn cec_repair_flagged_ptrs(c: *mut cec_codec, shards: *const *mut u8,
                                        d_flags: *const u8, nseg: usize, shard_len: usize,
                                        d_status: *mut u8, stream: *mut c_void) -> c_int;
+        pub fn cec_flag_status_multi(k: c_int, m: c_int, held: *const u8, flags: *const u8,
+                                     max_bad: c_int, status: *mut c_int, nlost: *mut c_int,
+                                     lost: *mut u8) -> c_int;
+        pub fn cec_flag_solve(k: c_int, m: c_int, held: *const u8, flags: *const u8,
+                              max_bad: c_int, status: *mut c_int, nout: *mut c_int,
+                              out_idx: *mut u8, in_idx: *mut u8, rows: *mut u8) -> c_int;
+        pub fn cec_repair_flagged_multi_ptrs(c: *mut cec_codec, shards: *const *mut u8,
+                                             d_flags: *const u8, nseg: usize, shard_len: usize,
+                                             max_bad: c_int, d_status: *mut u8,
+                                             stream: *mut c_void) -> c_int;
         pub fn cec_encode_idx_batch(c: *mut cec_codec, d_shard: *const u8,
                                     shard_seg_stride: usize, idx: c_int, d_parity: *mut u8,
                                     nseg: usize, shard_len: usize, accumulate: c_int,
@@ -404,6 +414,7 @@ pub const CEC_FLAG_CLEAN: c_int = 0;
 pub const CEC_FLAG_REBUILT: c_int = 1;
 pub const CEC_FLAG_MANY: c_int = 2;
 pub const CEC_FLAG_LOST: c_int = 3;
+pub const CEC_FLAG_MULTI_MAX: c_int = 4;
 pub const SEGMENT_COUNT: usize = 1000; // runtime/src/lib.rs:1026
 pub const FRAGMENT_COUNT: usize = 3; // runtime/src/lib.rs:1027
 
@@ -688,6 +699,43 @@ impl ReedSolomon {
                             &mut status, &mut lost)
         })?;
         Ok((status, if lost >= 0 { Some(lost as usize) } else { None }))
+    }
+
+    /// `repair_flagged_ptrs` for segments with several bad shards
+    /// (`cec_repair_flagged_multi_ptrs`): a segment with 1 to `max_bad` bad shards (at most
+    /// `CEC_FLAG_MULTI_MAX`) and at least k good ones has every bad shard rebuilt over its address,
+    /// from the first k good shards in index order; the decode rows are solved per segment on the
+    /// GPU. Arguments and stream behaviour as there (`flag_status_multi` states the rule).
+    ///
+    /// # Safety
+    /// As for `repair_flagged_ptrs`.
+    pub unsafe fn repair_flagged_multi_ptrs(&self, shards: &[*mut u8], d_flags: *const u8,
+                                            shard_len: usize, max_bad: i32, d_status: *mut u8,
+                                            stream: *mut c_void) -> Result<(), Error> {
+        let n = self.k + self.m;
+        if shards.len() % n != 0 {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        check(cec_repair_flagged_multi_ptrs(self.c, shards.as_ptr(), d_flags, shards.len() / n,
+                                            shard_len, max_bad as c_int, d_status, stream))
+    }
+
+    /// The rule `repair_flagged_multi_ptrs` applies to one segment (`cec_flag_status_multi`, host
+    /// only): returns the `CEC_FLAG_*` status and the ascending indices of the shards a
+    /// `CEC_FLAG_REBUILT` segment rewrites (empty for every other status).
+    pub fn flag_status_multi(&self, held: &[u8], flags: &[u8],
+                             max_bad: i32) -> Result<(i32, Vec<usize>), Error> {
+        let n = self.k + self.m;
+        if held.len() != n || flags.len() != n {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        let (mut status, mut nlost): (c_int, c_int) = (0, 0);
+        let mut lost = [0u8; CEC_FLAG_MULTI_MAX as usize];
+        check(unsafe {
+            cec_flag_status_multi(self.k as c_int, self.m as c_int, held.as_ptr(), flags.as_ptr(),
+                                  max_bad as c_int, &mut status, &mut nlost, lost.as_mut_ptr())
+        })?;
+        Ok((status, lost[..nlost as usize].iter().map(|&i| i as usize).collect()))
     }
 
     /// EncodeIdx on scattered device shards in place (`cec_encode_idx_ptrs`): `data` holds
