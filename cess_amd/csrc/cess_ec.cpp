@@ -2201,8 +2201,10 @@ void parity_column(const cec_codec* c, int idx, uint8_t* coef) {
 
 int check_acc_shape(size_t nseg, size_t shard_len) {
   if (int rc = check_batch(nseg, shard_len)) return rc;
-  if ((shard_len + 255) / 256 > 0x7fffffffull)
-    return set_err(CEC_EINVAL, "shard_len too large (> 512 GiB)");
+  // the byte path runs ceil(shard_len / 256) blocks of 256 in x, and HIP launches fewer than 2^32
+  // work items per dimension
+  if ((shard_len + 255) / 256 > 0xffffffull)
+    return set_err(CEC_EINVAL, "shard_len too large (> 4 GiB - 256)");
   return CEC_OK;
 }
 

@@ -16,27 +16,35 @@ template <bool V16>
 __global__ __launch_bounds__(256) void k_xor_reduce(uint8_t* __restrict__ dst,
                                                     const uint8_t* __restrict__ src, uint32_t nsrc,
                                                     uint64_t stride, uint64_t len) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if constexpr (V16) {
-    if (i * 16 >= len) return;
-    u32x4 acc = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(dst) + i);
-    for (uint32_t j = 0; j < nsrc; ++j)
-      acc ^= __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src + j * stride) + i);
-    __builtin_nontemporal_store(acc, reinterpret_cast<u32x4*>(dst) + i);
-  } else {
-    if (i >= len) return;
-    uint8_t acc = dst[i];
-    for (uint32_t j = 0; j < nsrc; ++j) acc ^= src[j * stride + i];
-    dst[i] = acc;
+  // a grid-stride walk: the launcher caps the grid (kXorMaxBlocks), one step for shorter buffers
+  const uint64_t step = (uint64_t)gridDim.x * 256;
+  const uint64_t n = V16 ? len / 16 : len;  // V16: len is a 16-byte multiple
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += step) {
+    if constexpr (V16) {
+      u32x4 acc = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(dst) + i);
+      for (uint32_t j = 0; j < nsrc; ++j)
+        acc ^= __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src + j * stride) + i);
+      __builtin_nontemporal_store(acc, reinterpret_cast<u32x4*>(dst) + i);
+    } else {
+      uint8_t acc = dst[i];
+      for (uint32_t j = 0; j < nsrc; ++j) acc ^= src[j * stride + i];
+      dst[i] = acc;
+    }
   }
 }
+
+// HIP refuses a launch of 2^32 or more work items in one dimension (gridDim.x * blockDim.x; the
+// byte path of a 4 GiB buffer is 2^24 blocks of 256), so the grid stops at 2^22 blocks and the
+// lanes walk the rest: 1 GiB of bytes, or 16 GiB of 16-byte columns, per step.
+constexpr uint64_t kXorMaxBlocks = 1u << 22;
 
 void launch_xor_reduce(uint8_t* dst, const uint8_t* src, uint32_t nsrc, uint64_t stride,
                        uint64_t len, hipStream_t st) {
   if (len == 0 || nsrc == 0) return;
   const bool v16 = (((uintptr_t)dst | (uintptr_t)src | stride | len) & 15) == 0;
   const uint64_t per_block = v16 ? 256 * 16 : 256;
-  const uint64_t blocks = (len + per_block - 1) / per_block;
+  uint64_t blocks = (len + per_block - 1) / per_block;
+  if (blocks > kXorMaxBlocks) blocks = kXorMaxBlocks;
   if (v16)
     hipLaunchKernelGGL(k_xor_reduce<true>, dim3((uint32_t)blocks), dim3(256), 0, st, dst, src,
                        nsrc, stride, len);

@@ -202,7 +202,9 @@ int cec_verify_ptrs(cec_codec* codec, const uint8_t* const* src, const uint8_t* 
                     size_t nseg, size_t shard_len, uint8_t* d_ok, void* hip_stream);
 /* GF(2^8) addition of device buffers: d_dst[0..len) ^= d_src[j*src_stride ..][0..len) for
  * j < nsrc (src_stride >= len when nsrc > 1). Enqueued on hip_stream, which must belong to the
- * device holding the buffers (no codec: the caller's current device and stream decide). */
+ * device holding the buffers (no codec: the caller's current device and stream decide). Any
+ * alignment; len up to 512 GiB (CEC_EINVAL past it) in one launch of a capped grid whose lanes
+ * walk the buffer, so lengths of 4 GiB and more run on the byte path too. */
 int cec_xor_batch(uint8_t* d_dst, const uint8_t* d_src, size_t nsrc, size_t src_stride,
                   size_t len, void* hip_stream);
 /* Partial rebuild of scattered shards, in place: cec_reconstruct_partial_batch without the batch.
@@ -394,8 +396,10 @@ int cec_repair_flagged_multi_ptrs(cec_codec* codec, uint8_t* const* shards, cons
  *  - Writes: the nseg * m * shard_len parity bytes, nothing else.
  *  - Validation happens before anything is enqueued; on any error no byte is written. CEC_EINVAL:
  *    codec or a needed pointer NULL, idx outside [0, k), nseg > 1 with shard_seg_stride <
- *    shard_len, or bytes the call reads overlapping the parity range it writes. CEC_ESHARDLEN:
- *    shard_len == 0. nseg == 0, or no flag set, is a no-op that returns CEC_OK.
+ *    shard_len, bytes the call reads overlapping the parity range it writes, or shard_len >
+ *    2^32 - 256 (the byte path's one launch per segment row: HIP takes fewer than 2^32 work items
+ *    per grid dimension). CEC_ESHARDLEN: shard_len == 0. nseg == 0, or no flag set, is a no-op
+ *    that returns CEC_OK.
  *  - Alignment: any alignment and any shard_len >= 1 is correct. When every base and stride is a
  *    16-byte multiple the kernels take 16-byte columns (a shard_len that is not gets a byte tail);
  *    otherwise the whole call runs byte-wise.
@@ -983,7 +987,13 @@ int cec_fill_synthetic(uint8_t* d_out, size_t seg_bytes, size_t nseg, uint64_t s
 #define CEC_OPT_FFTDEC_MODE 8   /* RS(32,32), rebuilds past CEC_OPT_FFTDEC_MIN: 0 = the cheapest
                                    of the FFT-domain decoders (syndrome rows, formal derivative) and
                                    the run-time matrix kernel by the cost model (default), 1 = always
-                                   the syndrome-row decoder, 2 = always the formal-derivative one */
+                                   the syndrome-row decoder, 2 = always the formal-derivative one.
+                                   Both FFT-domain decoders address a coset's 32 shards with 32-bit
+                                   buffer offsets, so they run only where shard_len is a multiple of
+                                   1024, every base is 16-byte aligned and the shard stride
+                                   (shard_len in the batch layout) is below 64 MiB (2^26); from
+                                   64 MiB on, whatever CEC_OPT_FFTDEC_MIN and this option say, the
+                                   run-time matrix kernels rebuild and the FFTDEC counters stay */
 int cec_set_option(cec_codec* codec, int option, int value);
 /* Counters (tests / monitoring). */
 #define CEC_STAT_DECODE_CACHED 1   /* erasure patterns in the decode cache */
