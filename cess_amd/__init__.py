@@ -6,11 +6,15 @@ plus the CESS segment / fragment records.
 """
 from . import audit, geometry, records
 from ._lib import (
+    CEC_CONFIRM_NONE,
+    CEC_CONFIRM_PROVEN,
+    CEC_CONFIRM_REFUTED,
     CEC_FLAG_CLEAN,
     CEC_FLAG_LOST,
     CEC_FLAG_MANY,
     CEC_FLAG_MULTI_MAX,
     CEC_FLAG_REBUILT,
+    CEC_HASHQ_SKIPPED,
 )
 from .hashq import HashQueue, sha256_blocks
 from .records import ErrTooManySegments
@@ -27,6 +31,8 @@ from .reedsolomon import (
     ErrTooFewShards,
     HipError,
     New,
+    confirm_flagged,
+    confirm_rule,
     decode_rows,
     fill_synthetic,
     flag_status,
@@ -43,4 +49,6 @@ __all__ = [
     "HashQueue", "sha256_blocks", "records", "ErrTooManySegments", "audit", "xor_batch",
     "ErrInvalidInput", "decode_rows", "flag_status", "CEC_FLAG_CLEAN", "CEC_FLAG_REBUILT",
     "CEC_FLAG_MANY", "CEC_FLAG_LOST", "CEC_FLAG_MULTI_MAX", "flag_status_multi",
+    "confirm_flagged", "confirm_rule", "CEC_CONFIRM_NONE", "CEC_CONFIRM_PROVEN",
+    "CEC_CONFIRM_REFUTED", "CEC_HASHQ_SKIPPED",
 ]

@@ -142,6 +142,14 @@ SIGNATURES = {
     "cec_hashq_add_check_concat_ptrs": (c_int, [c_void_p, POINTER(c_void_p), c_size_t, c_size_t,
                                                 c_size_t, c_size_t, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, POINTER(c_uint64)]),
+    "cec_hashq_add_check_where_ptrs": (c_int, [c_void_p, POINTER(c_void_p), c_size_t, c_size_t,
+                                               c_void_p, c_void_p, c_size_t, c_void_p, c_int,
+                                               c_void_p, c_void_p, POINTER(c_uint64)]),
+    "cec_hashq_where_plan": (c_int, [POINTER(c_uint8), POINTER(c_uint8), c_size_t, c_size_t,
+                                     POINTER(c_uint8), c_int, POINTER(c_uint32),
+                                     POINTER(c_size_t)]),
+    "cec_confirm_rule": (c_int, [c_int, c_int, POINTER(c_uint8), POINTER(c_int)]),
+    "cec_confirm_flagged": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
     "cec_hashq_tick": (c_int, [c_void_p, c_uint32]),
     "cec_hashq_finish": (c_int, [c_void_p]),
     "cec_hashq_status": (c_int, [c_void_p, c_uint64, POINTER(c_int), POINTER(c_size_t),
@@ -239,6 +247,10 @@ CEC_FLAG_REBUILT = 1
 CEC_FLAG_MANY = 2
 CEC_FLAG_LOST = 3
 CEC_FLAG_MULTI_MAX = 4
+CEC_CONFIRM_NONE = 0
+CEC_CONFIRM_PROVEN = 1
+CEC_CONFIRM_REFUTED = 2
+CEC_HASHQ_SKIPPED = 2
 CEC_HQOPT_TICK = 1
 CEC_PIPE_HASH_NONE = 0
 CEC_PIPE_HASH_GPU = 1

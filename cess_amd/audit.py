@@ -18,7 +18,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .reedsolomon import (Encoder, ErrInvalidInput, _dev_ptr, _on_gpu, _stream_handle, check)
+from .reedsolomon import (Encoder, ErrInvalidInput, _dev_ptr, _on_gpu, _stream_handle, check,
+                          confirm_flagged)
 
 CHUNK_COUNT = _lib.CEC_CHUNK_COUNT
 CHALLENGE_NEED = CHUNK_COUNT * 46 // 1000  # 47
@@ -161,10 +162,10 @@ def scrub_repair_multi_device(enc: Encoder, segments: Sequence, recorded,
     return _scrub_repair(enc, segments, recorded, queue, repair)
 
 
-def _scrub_repair(enc, segments, recorded, queue, repair):
-    """The scrub of the two calls above; repair(segments, d_flags, stream=...) ends it."""
+def _scrub_table(enc, segments, recorded):
+    """What the scrubs above hash: (segments as lists, their slots segment-major, the recorded
+    hashes slot by slot, the runs [a, b) of held slots, d_flags [nseg][k + m])."""
     import torch
-    from .hashq import HashQueue
     segments = [list(seg) for seg in segments]
     nseg, n = len(segments), enc.Shards
     if any(len(seg) != n for seg in segments):
@@ -191,6 +192,14 @@ def _scrub_repair(enc, segments, recorded, queue, repair):
             b += 1
         runs.append((a, b))
         a = b
+    return segments, slots, rec, runs, d_flags
+
+
+def _scrub_repair(enc, segments, recorded, queue, repair):
+    """The scrub of the two calls above; repair(segments, d_flags, stream=...) ends it."""
+    import torch
+    from .hashq import HashQueue
+    segments, slots, rec, runs, d_flags = _scrub_table(enc, segments, recorded)
 
     def go(q):
         flat = d_flags.view(-1)
@@ -204,5 +213,65 @@ def _scrub_repair(enc, segments, recorded, queue, repair):
         return d_flags, go(queue)
     held = sum(b - a for a, b in runs)
     cap = 1 << max(0, held - 1).bit_length()
+    dev = torch.device("cuda", enc.device)
     with HashQueue(capacity=cap, device=enc.device, stream=torch.cuda.current_stream(dev)) as q:
         return d_flags, go(q)
+
+
+def scrub_repair_confirm_device(enc: Encoder, segments: Sequence, recorded, max_bad: int = 1,
+                                queue=None):
+    """scrub_repair_device (max_bad == 1) or scrub_repair_multi_device (max_bad > 1) with the
+    proof the chain asks of restoral_order_complete: after the repair, exactly the fragments it
+    rewrote are hashed again and compared with their records, chosen on the GPU from d_flags and
+    d_status (HashQueue.add_check_where_ptrs over the whole [nseg][k + m] table, None where a shard
+    is not held, gated on CEC_FLAG_REBUILT), and confirm_flagged folds the result into one code
+    per segment. Arguments as in scrub_repair_device. Returns (d_flags, d_status,
+    d_ok [nseg][k + m], d_confirm [nseg]): d_ok is 1 where a rebuilt fragment now hashes to its record, 0 where it
+    still does not, CEC_HASHQ_SKIPPED everywhere else; d_confirm is CEC_CONFIRM_PROVEN for a healed
+    segment, CEC_CONFIRM_REFUTED where a record itself is wrong (the fragment is rebuilt to the
+    same bytes and fails again), CEC_CONFIRM_NONE for a segment that was not rebuilt. All on the
+    queue's stream, nothing waited for or copied out. A caller's queue, which has to be idle and
+    hold at least k + m chains, may be smaller than the table: the scrub runs in adds that fit
+    and the proof in slices of whole segments, each ticked to completion before the next. queue
+    None: a queue of the table's size on torch's current stream, owned and closed by the call."""
+    import torch
+    from .hashq import HashQueue
+    segments, slots, rec, runs, d_flags = _scrub_table(enc, segments, recorded)
+    nseg, n = len(segments), enc.Shards
+    dev = torch.device("cuda", enc.device)
+
+    def go(q):
+        stream = q.stream if q.stream is not None else 0  # a queue without one: the null stream
+        flat = d_flags.view(-1)
+        free = q.capacity
+        for a, b in runs:
+            while a < b:
+                if free == 0:
+                    q.finish()
+                    free = q.capacity
+                c = min(b, a + free)
+                q.add_check_ptrs(slots[a:c], rec[a:c], flat[a:c])
+                free -= c - a
+                a = c
+        q.finish()
+        if max_bad == 1:
+            d_status = enc.RepairFlaggedDevice(segments, d_flags, stream=stream)
+        else:
+            d_status = enc.RepairFlaggedMultiDevice(segments, d_flags, max_bad=max_bad,
+                                                    stream=stream)
+        d_ok = torch.empty((nseg, n), dtype=torch.uint8, device=dev)
+        ok = d_ok.view(-1)
+        step = max(1, q.capacity // n)  # whole segments per slice
+        for s0 in range(0, nseg, step):
+            s1 = min(nseg, s0 + step)
+            a, b = s0 * n, s1 * n
+            q.add_check_where_ptrs(slots[a:b], rec[a:b], flat[a:b], per=n, d_gate=d_status[s0:s1],
+                                   gate=_lib.CEC_FLAG_REBUILT, d_ok=ok[a:b])
+            q.finish()
+        return d_flags, d_status, d_ok, confirm_flagged(d_status, d_ok, n, stream=stream)
+
+    if queue is not None:
+        return go(queue)
+    cap = 1 << max(0, nseg * n - 1).bit_length()
+    with HashQueue(capacity=cap, device=enc.device, stream=torch.cuda.current_stream(dev)) as q:
+        return go(q)

@@ -33,6 +33,7 @@
 #include "fftdec_plan.h"
 #include "flag_solve.h"
 #include "gf256.h"
+#include "hashq_where.h"
 #include "host_util.h"
 #include "kernels.h"
 
@@ -2174,6 +2175,30 @@ int cec_xor_batch(uint8_t* d_dst, const uint8_t* d_src, size_t nsrc, size_t src_
   if (len == 0 || nsrc == 0) return CEC_OK;
   cec::launch_xor_reduce(d_dst, d_src, (uint32_t)nsrc, src_stride, len,
                          reinterpret_cast<hipStream_t>(hip_stream));
+  return check_launch();
+}
+
+// ---- what a scrub's repair proved (cec_hashq_add_check_where_ptrs's flags per segment) --------
+
+int cec_confirm_rule(int n, int status, const uint8_t* ok, int* confirm) {
+  if (n < 0 || (n && !ok) || !confirm) return set_err(CEC_EINVAL, "null or n < 0");
+  uint32_t zeros = 0, ones = 0;
+  for (int i = 0; i < n; ++i) {
+    zeros += ok[i] == 0;
+    ones += ok[i] == 1;
+  }
+  *confirm = (int)cec::confirm_rule(status == CEC_FLAG_REBUILT, zeros, ones);
+  return CEC_OK;
+}
+
+int cec_confirm_flagged(const uint8_t* d_status, const uint8_t* d_ok, size_t nseg, int n,
+                        uint8_t* d_confirm, void* hip_stream) {
+  if (n < 0 || (nseg && (!d_status || !d_confirm || (n && !d_ok))))
+    return set_err(CEC_EINVAL, "null buffer or n < 0");
+  if (nseg / 4 > 0x7fffffffull) return set_err(CEC_EINVAL, "nseg too large");
+  if (nseg == 0) return CEC_OK;
+  cec::launch_confirm_flagged(d_status, d_ok, nseg, (uint32_t)n, d_confirm,
+                              reinterpret_cast<hipStream_t>(hip_stream));
   return check_launch();
 }
 

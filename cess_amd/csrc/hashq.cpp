@@ -17,6 +17,7 @@
 
 #include "../../include/cess_ec.h"
 #include "hashq_ring.h"
+#include "hashq_where.h"
 #include "host_util.h"
 #include "kernels.h"
 
@@ -24,6 +25,7 @@ struct cec_hashq {
   int device = 0;
   hipStream_t stream = nullptr;
   cec::ShaChain* tab = nullptr;
+  uint32_t* totals = nullptr;  // two words behind the table: k_hashq_admit's running counts
   cec::HashqRing ring;  // which slots are live and how far along: all of the host's bookkeeping
   int tick_mode = 0;    // CEC_HQOPT_TICK
   uint32_t mask() const { return (uint32_t)(ring.cap - 1); }
@@ -167,12 +169,14 @@ int cec_hashq_create(int device, size_t capacity, void* hip_stream, cec_hashq** 
   // stream-ordered (hipFree would synchronise the whole device at destroy): every use of the
   // table is a launch on q->stream
   hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&q->tab),
-                                capacity * sizeof(cec::ShaChain), q->stream);
+                                capacity * sizeof(cec::ShaChain) + 2 * sizeof(uint32_t),
+                                q->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(q->stream);
   if (e != hipSuccess) {
     delete q;
     return cec::set_error(CEC_ENOMEM, std::string("hashq table: ") + hipGetErrorString(e));
   }
+  q->totals = reinterpret_cast<uint32_t*>(q->tab + capacity);
   *out = q;
   return CEC_OK;
 }
@@ -252,6 +256,40 @@ int cec_hashq_add_check_concat_ptrs(cec_hashq* q, const uint8_t* const* d_parts,
   // one buffer per chain is cec_hashq_add_ptrs: any len, part_len not used, no prefix to give
   if (parts == 1 && !d_prefix_hex) return add_ptrs(q, d_parts, n, len, d_hex, c, ticket);
   return add_concat_ptrs(q, d_parts, n, parts, part_len, len, d_hex, d_prefix_hex, c, ticket);
+}
+
+static_assert(CEC_HASHQ_SKIPPED == cec::kWhereSkipped && CEC_CONFIRM_NONE == cec::kConfirmNone &&
+                  CEC_CONFIRM_PROVEN == cec::kConfirmProven &&
+                  CEC_CONFIRM_REFUTED == cec::kConfirmRefuted,
+              "hashq_where.h restates the codes of cess_ec.h");
+
+int cec_hashq_add_check_where_ptrs(cec_hashq* q, const uint8_t* const* d_bufs, size_t n, size_t len,
+                                   const uint8_t* d_expect, const uint8_t* d_flags, size_t per,
+                                   const uint8_t* d_gate, int gate, uint8_t* d_ok, uint8_t* d_hex,
+                                   uint64_t* ticket) {
+  int rc = check_args(q, n, d_expect, d_ok);
+  if (rc) return rc;
+  if (n && (!d_bufs || !d_flags)) return cec::set_error(CEC_EINVAL, "null");
+  if (d_gate && per == 0) return cec::set_error(CEC_EINVAL, "gate bytes need per > 0");
+  if (gate < 0 || gate > 255) return cec::set_error(CEC_EINVAL, "gate must be a byte value");
+  if (n > 0xFFFFFFFFull) return cec::set_error(CEC_EINVAL, "n too large");
+  // i < 2^32 - 1, so any per from 2^32 - 1 on puts every chain in group 0
+  const uint32_t per32 = (uint32_t)(per < 0xFFFFFFFFull ? per : 0xFFFFFFFFull);
+  // the host knows no chain's fate: n slots, n chains of the whole length, a plain add
+  return add_chains(q, n, cec::sha256_blocks(len), ticket, [&](uint64_t slot0) {
+    cec::launch_hashq_admit(q->tab, q->mask(), slot0, n, d_bufs, len, d_expect, d_flags, per32,
+                            d_gate, (uint32_t)gate, d_ok, d_hex, q->totals, q->stream);
+  });
+}
+
+int cec_hashq_where_plan(const uint8_t* held, const uint8_t* flags, size_t n, size_t per,
+                         const uint8_t* gate_bytes, int gate, uint32_t* pos, size_t* nsel) {
+  if (n && (!held || !flags || !pos)) return cec::set_error(CEC_EINVAL, "null");
+  if (gate_bytes && per == 0) return cec::set_error(CEC_EINVAL, "gate bytes need per > 0");
+  if (gate < 0 || gate > 255) return cec::set_error(CEC_EINVAL, "gate must be a byte value");
+  if (n > 0xFFFFFFFFull) return cec::set_error(CEC_EINVAL, "n too large");
+  cec::where_plan(held, flags, n, per, gate_bytes, (uint32_t)gate, pos, nsel);
+  return CEC_OK;
 }
 
 int cec_hashq_tick(cec_hashq* q, uint32_t max_blocks) {

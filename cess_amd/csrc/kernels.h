@@ -270,6 +270,22 @@ void launch_hashq_add_concat(ShaChain* tab, uint32_t mask, uint64_t slot0, uint6
 // chains are not based on.
 void launch_hashq_rebase(ShaChain* tab, uint32_t mask, uint64_t slot0, uint64_t n,
                          const uint8_t* const* addr, size_t stride, uint64_t off, hipStream_t st);
+// Checked chains the device admits (cec_hashq_add_check_where_ptrs): n chains over src[0 .. n) (a
+// HOST array, null entries allowed) take the n slots slot0.., chain i admitted iff src[i] is set,
+// flags[i] == 0 and (gate_bytes null or gate_bytes[i / per] == gate), read on the device when the
+// stream gets there. Admitted chains take the front slots in index order, checked against
+// expect + 64 * i into ok + i, hex (if set) to hex + 64 * i; the others are parked complete in the
+// back slots and get ok[i] = 2. totals: two words of device memory for the launches' running
+// counts. One launch per 256 chains, ordered on st; stops at a launch that fails.
+void launch_hashq_admit(ShaChain* tab, uint32_t mask, uint64_t slot0, uint64_t n,
+                        const uint8_t* const* src, uint64_t len, const uint8_t* expect,
+                        const uint8_t* flags, uint32_t per, const uint8_t* gate_bytes,
+                        uint32_t gate, uint8_t* ok, uint8_t* hex, uint32_t* totals,
+                        hipStream_t st);
+// cec_confirm_flagged: confirm[s] from status[s] and ok[s * n .. s * n + n) (hashq_where.h
+// confirm_rule), one wave per segment.
+void launch_confirm_flagged(const uint8_t* status, const uint8_t* ok, uint64_t nseg, uint32_t n,
+                            uint8_t* confirm, hipStream_t st);
 // Advance the n chains in slots head.. by at most max_blocks blocks each; tick_mode 0 lets `live`
 // (chains not yet complete among them) pick the kernel form, 1 or 2 = two waves with that many
 // blocks prefetched, 3 = one wave per 64 chains.

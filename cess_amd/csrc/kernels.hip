@@ -24,6 +24,7 @@
 #include "dev_util.h"
 #include "flag_solve.h"
 #include "gf256.h"
+#include "hashq_where.h"
 #include "kernels.h"
 
 namespace cec {
@@ -2150,6 +2151,38 @@ void launch_flag_plan_multi(const FlagPlanMulti& p, hipStream_t st) {
   if (p.nseg == 0) return;
   hipLaunchKernelGGL(k_flag_plan_multi, dim3((unsigned)(((uint64_t)p.nseg + 3) / 4)), dim3(256), 0,
                      st, p);
+}
+
+// cec_confirm_flagged: what the checked chains of the rebuilt fragments proved, per segment. One
+// wave per segment, four segments per workgroup; the lanes stride over the segment's n ok bytes
+// and ballots count its zeros and ones (a skipped chain's 2 counts as neither). A segment that is
+// not REBUILT is decided by its status byte: none of its ok bytes is read.
+__global__ __launch_bounds__(256) void k_confirm_flagged(const uint8_t* __restrict__ status,
+                                                         const uint8_t* __restrict__ ok,
+                                                         uint64_t nseg, uint32_t n,
+                                                         uint8_t* __restrict__ confirm) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t s = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= nseg) return;  // the whole wave
+  const bool rebuilt = status[s] == kFlagRebuilt;
+  uint32_t zeros = 0, ones = 0;
+  if (rebuilt) {
+    const uint8_t* __restrict__ o = ok + s * n;
+    for (uint32_t base = 0; base < n; base += 64) {
+      const uint32_t i = base + lane;
+      const uint32_t v = i < n ? o[i] : kWhereSkipped;
+      zeros += (uint32_t)__popcll(__ballot(v == 0));
+      ones += (uint32_t)__popcll(__ballot(v == 1));
+    }
+  }
+  if (lane == 0) confirm[s] = (uint8_t)confirm_rule(rebuilt, zeros, ones);
+}
+
+void launch_confirm_flagged(const uint8_t* status, const uint8_t* ok, uint64_t nseg, uint32_t n,
+                            uint8_t* confirm, hipStream_t st) {
+  if (nseg == 0) return;
+  hipLaunchKernelGGL(k_confirm_flagged, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, st,
+                     status, ok, nseg, n, confirm);
 }
 
 }  // namespace cec

@@ -2,9 +2,11 @@
 // SegmentList (c-pallets/file-bank/src/types.rs:13-16): one-shot batch kernels (k_sha256,
 // k_sha256_2w) and the streaming hash-queue kernels: the ticks (k_sha256_tick), and the adds
 // (k_hashq_add for strided chains, k_hashq_add_concat for chains by address), which write their
-// chain records through one initialiser (sha_chain), and k_hashq_rebase. The ticks share one
+// chain records through one initialiser (sha_chain), k_hashq_rebase, and k_hashq_admit for checked
+// chains the device admits (packed into the add's front slots, hashq_where.h). The ticks share one
 // finisher (sha_finish): the hex of a completed chain and its check against a recorded hash.
 #include "dev_util.h"
+#include "hashq_where.h"
 #include "kernels.h"
 
 namespace cec {
@@ -974,6 +976,71 @@ __global__ __launch_bounds__(256) void k_hashq_rebase(HashqRebaseArgs a) {
   a.tab[(uint32_t)(a.slot0 + i) & a.mask].src = (const uint8_t*)(uintptr_t)(K->addr[i] - a.off);
 }
 
+// Checked chains the device admits (cec_hashq_add_check_where_ptrs; rule and placement in
+// hashq_where.h). One launch per kWhereChunk chains of the add, in index order on the queue's
+// stream; slot0, n, ok, expect, hex and gate_bytes are the add's, chain i0 + t being lane t's.
+// A tick wave costs the same whatever its live lanes, so the admitted chains are packed into
+// the add's front slots and the rest parked behind them: a parked record has blk at its chain's
+// block count, which every tick form takes for complete (no block produced or consumed, no
+// finisher, src never read), and its ok byte gets CEC_HASHQ_SKIPPED here. A group of 64 slots
+// that holds only parked chains leaves each tick launch after its record loads.
+// totals: the admitted and parked counts of the launches before this one of the same add, two
+// words the queue owns. The launches of an add are ordered, so plain loads and stores do.
+struct HashqAdmitArgs {
+  ShaChain* tab;
+  uint64_t slot0;
+  uint64_t len;
+  uint8_t* hex;
+  const uint8_t* expect;
+  uint8_t* ok;
+  const uint8_t* flags;
+  const uint8_t* gate_bytes;
+  uint32_t* totals;
+  uint32_t mask, n, i0, cnt, per, gate;
+  uint64_t addr[kHashqAddrs];
+};
+static_assert(sizeof(HashqAdmitArgs) <= 2048 + 128, "a 2 KiB argument block plus the scalars");
+static_assert(kWhereChunk == kHashqAddrs, "one launch takes one argument block of addresses");
+typedef const HashqAdmitArgs __attribute__((address_space(4))) HashqAdmitArgsK;
+
+__global__ __launch_bounds__(256) void k_hashq_admit(HashqAdmitArgs a) {
+  const HashqAdmitArgsK* __restrict__ K =
+      (const HashqAdmitArgsK*)__builtin_amdgcn_kernarg_segment_ptr();
+  __shared__ uint32_t count[kWhereWaves];
+  const uint32_t t = threadIdx.x, wave = t / kWhereWave;
+  const bool mine = t < a.cnt;
+  const uint32_t i = a.i0 + t;  // the chain's index in the add
+  const uint64_t src = mine ? K->addr[t] : 0;
+  bool adm = false;
+  if (mine && src)  // a chain without a buffer is decided: its flag and gate bytes are not read
+    adm = where_admit(true, a.flags[i], a.gate_bytes != nullptr,
+                      a.gate_bytes ? a.gate_bytes[i / a.per] : 0, a.gate);
+  const unsigned long long ballot = __ballot(adm);
+  const uint32_t rank_in_wave = __builtin_amdgcn_mbcnt_hi(
+      (uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0));
+  if ((t & (kWhereWave - 1)) == 0) count[wave] = where_count(ballot);
+  // the first launch of an add starts the totals; a later one reads what the one before left
+  const uint32_t sel_before = a.i0 ? a.totals[0] : 0, park_before = a.i0 ? a.totals[1] : 0;
+  __syncthreads();  // the waves' counts are written, the totals are read
+  const uint32_t cw[kWhereWaves] = {count[0], count[1], count[2], count[3]};
+  if (t == 0) {
+    const uint32_t sel = where_waves_before(cw, kWhereWaves);
+    a.totals[0] = sel_before + sel;
+    a.totals[1] = park_before + a.cnt - sel;
+  }
+  if (!mine) return;
+  const uint32_t pos = where_pos(adm, a.n, sel_before, park_before, t,
+                                 where_waves_before(cw, wave) + rank_in_wave);
+  ShaChain c = sha_chain((const uint8_t*)(uintptr_t)src, a.len, 0,
+                         adm && a.hex ? a.hex + (uint64_t)i * 64 : nullptr, 0, nullptr,
+                         a.expect + (uint64_t)i * 64, adm ? a.ok + i : nullptr);
+  if (!adm) {
+    c.blk = sha256_blocks(a.len);
+    a.ok[i] = (uint8_t)kWhereSkipped;
+  }
+  a.tab[(uint32_t)(a.slot0 + pos) & a.mask] = c;
+}
+
 void launch_sha256_hex(int sha_mode, const uint8_t* const* ptrs, const Layout* L, int nshards,
                        uint64_t n, uint64_t len, uint8_t* hex_out, hipStream_t st) {
   if (n == 0) return;
@@ -1051,6 +1118,32 @@ void launch_hashq_rebase(ShaChain* tab, uint32_t mask, uint64_t slot0, uint64_t 
     a.slot0 = slot0 + i0;
     a.n = cnt;
     hipLaunchKernelGGL(k_hashq_rebase, dim3(1), dim3(256), 0, st, a);
+  });
+}
+
+void launch_hashq_admit(ShaChain* tab, uint32_t mask, uint64_t slot0, uint64_t n,
+                        const uint8_t* const* src, uint64_t len, const uint8_t* expect,
+                        const uint8_t* flags, uint32_t per, const uint8_t* gate_bytes,
+                        uint32_t gate, uint8_t* ok, uint8_t* hex, uint32_t* totals,
+                        hipStream_t st) {
+  HashqAdmitArgs a;
+  a.tab = tab;
+  a.slot0 = slot0;
+  a.len = len;
+  a.hex = hex;
+  a.expect = expect;
+  a.ok = ok;
+  a.flags = flags;
+  a.gate_bytes = gate_bytes;
+  a.totals = totals;
+  a.mask = mask;
+  a.n = (uint32_t)n;
+  a.per = per;
+  a.gate = gate;
+  for_addr_chunks(n, src, 1, a.addr, [&](uint64_t i0, uint32_t cnt) {
+    a.i0 = (uint32_t)i0;
+    a.cnt = cnt;
+    hipLaunchKernelGGL(k_hashq_admit, dim3(1), dim3(256), 0, st, a);
   });
 }
 

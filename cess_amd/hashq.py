@@ -281,6 +281,43 @@ class HashQueue:
             self._kept.append((t.value, up))
         return t.value, d_ok
 
+    def add_check_where_ptrs(self, tensors, expect, d_flags, per: int = 1, d_gate=None,
+                             gate: int = 0, d_ok=None, d_hex=None):
+        """`add_check_ptrs` whose chains the GPU admits (cec_hashq_add_check_where_ptrs): chain i
+        runs iff tensors[i] is not None, d_flags[i] == 0 and (d_gate is None or
+        d_gate[i // per] == gate), decided by the add's kernels from the uint8 device tensors
+        d_flags [n] and d_gate when the queue's stream gets there, so both may still be in
+        production on that stream (a scrub's flags and a repair's statuses: with per = k + m and
+        gate = CEC_FLAG_REBUILT, the fragments the repair just rewrote). An admitted chain is
+        compared with expect[i] and flagged 1 or 0 in d_ok[i] by the tick launch that completes
+        it, its hex, with d_hex, at d_hex + 64 * i; every other chain gets d_ok[i] =
+        CEC_HASHQ_SKIPPED from the add, no byte of its tensor is read and its hex is not written.
+        `tensors` may hold None; the others are 1-D uint8 device tensors of one length (else
+        ErrShardSize). `expect` as in `add_check_ptrs`: a list is uploaded once and kept until
+        the add is complete. The add takes len(tensors) slots of the ring whatever is admitted.
+        d_ok None: a new uint8 device tensor [n]. Nothing waits. Returns (ticket, d_ok)."""
+        tensors = list(tensors)
+        n = len(tensors)
+        sizes = {t.numel() for t in tensors if t is not None}
+        if len(sizes) > 1:
+            raise ErrShardSize(ErrShardSize.__doc__)
+        d_ok = self._ok(d_ok, n)
+        if n == 0:
+            return 0, d_ok
+        if d_flags is None or d_flags.numel() < n or \
+                (d_gate is not None and per > 0 and d_gate.numel() < (n + per - 1) // per):
+            raise ErrShardSize(ErrShardSize.__doc__)
+        exp, up = self._expect(expect, n)
+        ptrs = (c_void_p * n)(*[_at(t) for t in tensors])
+        t = c_uint64()
+        check(_lib.load().cec_hashq_add_check_where_ptrs(
+            self._h, ptrs, n, sizes.pop() if sizes else 0, exp, _dev_ptr(d_flags), per,
+            _at(d_gate), gate, _dev_ptr(d_ok), _at(d_hex), byref(t)),
+            "HashQueue.add_check_where_ptrs")
+        if up is not None:
+            self._kept.append((t.value, up))
+        return t.value, d_ok
+
     def add_fragments(self, d_data, d_parity, nseg: int, k: int, m: int, shard_len: int,
                       d_hex, with_parity: bool = True) -> int:
         """Hash every fragment of a batch ([nseg][k][len] data, [nseg][m][len] parity) into

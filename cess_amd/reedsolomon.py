@@ -964,6 +964,42 @@ def flag_status_multi(data_shards: int, parity_shards: int, held, flags, max_bad
     return status.value, [int(x) for x in lost[:nlost.value]]
 
 
+def confirm_rule(status: int, ok) -> int:
+    """Host only (cec_confirm_rule): what confirm_flagged computes for one segment from its
+    CEC_FLAG_* status and its k+m ok bytes (1 match, 0 mismatch, CEC_HASHQ_SKIPPED not hashed).
+    Returns CEC_CONFIRM_NONE unless the status is CEC_FLAG_REBUILT; then REFUTED if any byte is 0,
+    else PROVEN if any is 1, else NONE."""
+    o = np.ascontiguousarray(np.asarray(ok, dtype=np.uint8))
+    if o.ndim != 1:
+        raise ValueError("ok must be one segment's bytes")
+    out = c_int(-1)
+    check(_lib.load().cec_confirm_rule(o.size, status, o.ctypes.data_as(POINTER(c_uint8)),
+                                       byref(out)), "confirm_rule")
+    return out.value
+
+
+def confirm_flagged(d_status, d_ok, n: int, d_confirm=None, stream=None):
+    """What a repair proved, per segment, on the GPU (cec_confirm_flagged): d_status is the uint8
+    device tensor [nseg] of CEC_FLAG_* codes a flagged repair left, d_ok [nseg][n] the flags of
+    HashQueue.add_check_where_ptrs over the rebuilt fragments. Returns the uint8 device tensor
+    [nseg] (d_confirm, or a new one) of CEC_CONFIRM_* codes by the rule of `confirm_rule`:
+    PROVEN where every rebuilt fragment of a REBUILT segment hashes to its record, REFUTED where
+    one still does not (the record is wrong), NONE elsewhere. Enqueued on `stream` and not waited
+    for; only d_confirm is written."""
+    import torch
+    nseg = d_status.numel()
+    if d_ok.numel() < nseg * n:
+        raise ErrShardSize(ErrShardSize.__doc__)
+    if d_confirm is None:
+        d_confirm = torch.empty(nseg, dtype=torch.uint8, device=d_status.device)
+    elif d_confirm.numel() < nseg:
+        raise ErrShardSize(ErrShardSize.__doc__)
+    check(_lib.load().cec_confirm_flagged(_dev_ptr(d_status), _dev_ptr(d_ok), nseg, n,
+                                          _dev_ptr(d_confirm), _stream_handle(stream)),
+          "confirm_flagged")
+    return d_confirm
+
+
 def fill_synthetic(d_out, seg_bytes: int, nseg: int, seg0: int, seed: int, stream=None) -> None:
     """Counter-based synthetic segments in HBM (SURVEY.md §8d input generator)."""
     check(_lib.load().cec_fill_synthetic(_dev_ptr(d_out), seg_bytes, nseg, seg0, seed,

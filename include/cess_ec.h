@@ -382,6 +382,29 @@ int cec_flag_solve(int k, int m, const uint8_t* held, const uint8_t* flags, int 
 int cec_repair_flagged_multi_ptrs(cec_codec* codec, uint8_t* const* shards, const uint8_t* d_flags,
                                   size_t nseg, size_t shard_len, int max_bad, uint8_t* d_status,
                                   void* hip_stream);
+/* What a repair proved, per segment: the close of restoral_order_complete, which the chain accepts
+ * only if the regenerated fragment hashes to its recorded fragment_hash. After the repairs above,
+ * cec_hashq_add_check_where_ptrs (cess_ec.h below) re-hashes exactly the rebuilt fragments; this
+ * folds its flags into one code per segment, which keeps "was bad, is healed" apart from "the
+ * record itself is wrong" (such a fragment is rebuilt to the same bytes and fails again). */
+#define CEC_CONFIRM_NONE 0    /* segment not CEC_FLAG_REBUILT: nothing to prove */
+#define CEC_CONFIRM_PROVEN 1  /* every rebuilt fragment hashes to its record */
+#define CEC_CONFIRM_REFUTED 2 /* some rebuilt fragment still does not: the record is wrong */
+/* Host only: the rule for one segment. ok: its n bytes as the where-add leaves them (1 match, 0
+ * mismatch, CEC_HASHQ_SKIPPED not hashed). status != CEC_FLAG_REBUILT: CEC_CONFIRM_NONE. Otherwise
+ * REFUTED if any byte is 0, else PROVEN if any is 1, else NONE. CEC_EINVAL: n < 0, a NULL ok with
+ * n > 0, a NULL confirm. */
+int cec_confirm_rule(int n, int status, const uint8_t* ok, int* confirm);
+/* The rule on the GPU: d_confirm[s] from d_status[s] and d_ok[s*n .. s*n+n), all DEVICE memory of
+ * any alignment, nseg segments, one wave per segment. Enqueued on hip_stream on the current device,
+ * as cec_xor_batch, and not waited for; d_status and d_ok may still be in production by work
+ * queued earlier on that stream.
+ *  - Reads: d_status, and d_ok of the CEC_FLAG_REBUILT segments only. Writes: d_confirm and nothing
+ *    else; d_status keeps its four codes.
+ *  - Validation: before anything is enqueued. CEC_EINVAL: n < 0; with nseg > 0 a NULL d_status or
+ *    d_confirm, or a NULL d_ok with n > 0; nseg >= 2^33. nseg == 0: CEC_OK. */
+int cec_confirm_flagged(const uint8_t* d_status, const uint8_t* d_ok, size_t nseg, int n,
+                        uint8_t* d_confirm, void* hip_stream);
 /* ---- parity accumulated shard by shard (klauspost EncodeIdx and Update) -----------------------
  * Both are one primitive on the codec's encode matrix E (cec_matrix; row k+o is parity shard o):
  *   parity[o] ^= E[k+o][j] * x_j   for every o < m,
@@ -626,6 +649,48 @@ int cec_hashq_add_check_concat_ptrs(cec_hashq* q, const uint8_t* const* d_parts,
                                     size_t parts, size_t part_len, size_t len,
                                     const uint8_t* d_expect, uint8_t* d_ok, uint8_t* d_hex,
                                     uint8_t* d_prefix_hex, uint64_t* ticket);
+/* cec_hashq_add_check_concat_ptrs at parts == 1 whose chains the DEVICE admits: the proof of a
+ * repair, which hashes only what was rebuilt, the list of which exists only in HBM. d_bufs: a HOST
+ * array of n DEVICE pointers of len bytes each, NULL entries allowed. d_flags: n DEVICE bytes, any
+ * alignment. d_gate: DEVICE bytes, one per `per` chains, or NULL. Chain i is admitted iff
+ *   d_bufs[i] != NULL && d_flags[i] == 0 && (d_gate == NULL || d_gate[i / per] == gate).
+ * With the d_flags of a scrub, per = k+m, d_gate = the d_status of cec_repair_flagged_ptrs and
+ * gate = CEC_FLAG_REBUILT that is "the fragments the repair just rewrote".
+ *  - Admitted chain: hashes its len bytes in place; the tick launch that completes it writes
+ *    d_ok[i] = 1 or 0 against d_expect + 64 * i (as cec_hashq_add_check) and, with d_hex, its hex
+ *    to d_hex + 64 * i.
+ *  - Chain not admitted: the add's kernel writes d_ok[i] = CEC_HASHQ_SKIPPED; no byte at d_bufs[i]
+ *    is read, its hex is not written, and it costs the ticks a record load. The flag and gate
+ *    bytes of a NULL entry are not read.
+ *  - Reads: d_flags and d_gate by the add's kernels, when the queue's stream gets there: they may
+ *    still be in production by work queued earlier on that stream. Not waited for: nothing is
+ *    synchronised or copied to the host; d_bufs belongs to the caller again on return (the
+ *    addresses travel in kernel arguments, 256 per launch).
+ *  - Packing: a tick wave costs the same with one live lane as with 64, so the admitted chains
+ *    take the add's first slots in index order and the others are parked, complete, in its last;
+ *    a group of 64 slots without an admitted chain leaves every tick after its record loads.
+ *    The ok, expect and hex addresses travel with the chain, so the order is invisible outside.
+ *  - Host bookkeeping: the host cannot know what the device admits. The add takes n ring slots
+ *    and is tracked as n chains of len's blocks: cec_hashq_status reports it so, it is complete
+ *    when such an add would be, and CEC_ENOMEM is returned when n slots do not fit.
+ *  - Validation: before anything is enqueued; on an error the ring is unchanged and no byte is
+ *    written. CEC_EINVAL: a NULL queue; with n > 0 a NULL d_bufs, d_expect, d_flags or d_ok;
+ *    d_expect not 4-byte aligned; d_gate set with per == 0; gate outside 0..255; n > 2^32 - 1.
+ *    n == 0: CEC_OK, ticket 0. */
+#define CEC_HASHQ_SKIPPED 2 /* d_ok value of a chain the device did not admit */
+int cec_hashq_add_check_where_ptrs(cec_hashq* q, const uint8_t* const* d_bufs, size_t n, size_t len,
+                                   const uint8_t* d_expect, const uint8_t* d_flags, size_t per,
+                                   const uint8_t* d_gate, int gate, uint8_t* d_ok, uint8_t* d_hex,
+                                   uint64_t* ticket);
+/* Host only: where the add above puts its chains. held[i] != 0 stands for d_bufs[i] != NULL; flags,
+ * per, gate_bytes (may be NULL) and gate as there, in host memory. pos[i] (n words) receives chain
+ * i's slot offset within the add, *nsel (may be NULL) the admitted count: the admitted chains hold
+ * offsets [0, nsel) in index order, the others [nsel, n) descending. The function runs the admit
+ * kernel's own arithmetic (csrc/hashq_where.h) with loops in place of lanes, in the kernel's
+ * chunks of 256 and waves of 64. CEC_EINVAL: with n > 0 a NULL held, flags or pos; gate_bytes set
+ * with per == 0; gate outside 0..255; n > 2^32 - 1. */
+int cec_hashq_where_plan(const uint8_t* held, const uint8_t* flags, size_t n, size_t per,
+                         const uint8_t* gate_bytes, int gate, uint32_t* pos, size_t* nsel);
 /* Advance every live chain by at most max_blocks 64-byte blocks (0 = to completion). */
 int cec_hashq_tick(cec_hashq* q, uint32_t max_blocks);
 /* Tick until every chain added so far is complete (enqueued; synchronise the stream to wait). */

@@ -253,6 +253,18 @@ pub mod sys {
                                                len: usize, d_expect: *const u8, d_ok: *mut u8,
                                                d_hex: *mut u8, d_prefix_hex: *mut u8,
                                                ticket: *mut u64) -> c_int;
+        pub fn cec_hashq_add_check_where_ptrs(q: *mut cec_hashq, d_bufs: *const *const u8,
+                                              n: usize, len: usize, d_expect: *const u8,
+                                              d_flags: *const u8, per: usize, d_gate: *const u8,
+                                              gate: c_int, d_ok: *mut u8, d_hex: *mut u8,
+                                              ticket: *mut u64) -> c_int;
+        pub fn cec_hashq_where_plan(held: *const u8, flags: *const u8, n: usize, per: usize,
+                                    gate_bytes: *const u8, gate: c_int, pos: *mut u32,
+                                    nsel: *mut usize) -> c_int;
+        pub fn cec_confirm_rule(n: c_int, status: c_int, ok: *const u8,
+                                confirm: *mut c_int) -> c_int;
+        pub fn cec_confirm_flagged(d_status: *const u8, d_ok: *const u8, nseg: usize, n: c_int,
+                                   d_confirm: *mut u8, stream: *mut c_void) -> c_int;
         pub fn cec_hashq_tick(q: *mut cec_hashq, max_blocks: u32) -> c_int;
         pub fn cec_hashq_finish(q: *mut cec_hashq) -> c_int;
         pub fn cec_hashq_status(q: *const cec_hashq, ticket: u64, done: *mut c_int,
@@ -415,6 +427,10 @@ pub const CEC_FLAG_REBUILT: c_int = 1;
 pub const CEC_FLAG_MANY: c_int = 2;
 pub const CEC_FLAG_LOST: c_int = 3;
 pub const CEC_FLAG_MULTI_MAX: c_int = 4;
+pub const CEC_CONFIRM_NONE: c_int = 0;
+pub const CEC_CONFIRM_PROVEN: c_int = 1;
+pub const CEC_CONFIRM_REFUTED: c_int = 2;
+pub const CEC_HASHQ_SKIPPED: u8 = 2;
 pub const SEGMENT_COUNT: usize = 1000; // runtime/src/lib.rs:1026
 pub const FRAGMENT_COUNT: usize = 3; // runtime/src/lib.rs:1027
 
@@ -891,6 +907,52 @@ pub unsafe fn hashq_add_check_concat_ptrs(q: *mut sys::cec_hashq, d_parts: &[*co
                                                part_len, len, d_expect, d_ok, d_hex,
                                                d_prefix_hex, &mut ticket))?;
     Ok(ticket)
+}
+
+/// `hashq_add_check_concat_ptrs` at `parts == 1` whose chains the GPU admits
+/// (`cec_hashq_add_check_where_ptrs`): chain i runs iff `d_bufs[i]` is not null, `d_flags[i] == 0`
+/// and (`d_gate` is null or `d_gate[i / per] == gate`), read from device memory when the queue's
+/// stream gets there. An admitted chain writes 1 or 0 to `d_ok + i` against `d_expect + 64 * i`;
+/// every other chain gets `CEC_HASHQ_SKIPPED` there and none of its bytes is read. With a scrub's
+/// flags, `per = k + m`, `d_gate` the statuses of `repair_flagged_ptrs` and `gate =
+/// CEC_FLAG_REBUILT`: the fragments the repair just rewrote. Returns the add's ticket.
+///
+/// # Safety
+/// As `hashq_add_check_concat_ptrs`; `d_flags` (one byte per chain) and `d_gate` (one per `per`
+/// chains, or null) must be device memory valid until the add's kernels have run.
+pub unsafe fn hashq_add_check_where_ptrs(q: *mut sys::cec_hashq, d_bufs: &[*const u8], len: usize,
+                                         d_expect: *const u8, d_flags: *const u8, per: usize,
+                                         d_gate: *const u8, gate: u8, d_ok: *mut u8,
+                                         d_hex: *mut u8) -> Result<u64, Error> {
+    let mut ticket = 0u64;
+    check(sys::cec_hashq_add_check_where_ptrs(q, d_bufs.as_ptr(), d_bufs.len(), len, d_expect,
+                                              d_flags, per, d_gate, gate as c_int, d_ok, d_hex,
+                                              &mut ticket))?;
+    Ok(ticket)
+}
+
+/// What a repair proved, per segment, on the GPU (`cec_confirm_flagged`): `d_confirm[s]` becomes a
+/// `CEC_CONFIRM_*` code from `d_status[s]` and the `n` bytes at `d_ok + s * n` that
+/// `hashq_add_check_where_ptrs` left (`confirm_rule` states the rule). Enqueued on `stream`, not
+/// waited for; only `d_confirm` is written.
+///
+/// # Safety
+/// `d_status` and `d_confirm` must be device memory of `nseg` bytes, `d_ok` of `nseg * n`, valid
+/// until the stream has run the kernel; `stream` a HIP stream of the current device or null.
+pub unsafe fn confirm_flagged(d_status: *const u8, d_ok: *const u8, nseg: usize, n: usize,
+                              d_confirm: *mut u8, stream: *mut c_void) -> Result<(), Error> {
+    check(sys::cec_confirm_flagged(d_status, d_ok, nseg, n as c_int, d_confirm, stream))
+}
+
+/// The rule of `confirm_flagged` for one segment (`cec_confirm_rule`, host only): `CEC_CONFIRM_NONE`
+/// unless `status` is `CEC_FLAG_REBUILT`; then `REFUTED` if any byte of `ok` is 0, else `PROVEN`
+/// if any is 1, else `NONE`.
+pub fn confirm_rule(status: c_int, ok: &[u8]) -> Result<c_int, Error> {
+    let mut confirm: c_int = -1;
+    check(unsafe {
+        sys::cec_confirm_rule(ok.len() as c_int, status, ok.as_ptr(), &mut confirm)
+    })?;
+    Ok(confirm)
 }
 
 /// One segment's SegmentList hashes: 64 hex chars for the segment, k+m for its fragments.
