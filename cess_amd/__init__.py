@@ -37,6 +37,7 @@ from .reedsolomon import (
     fill_synthetic,
     flag_status,
     flag_status_multi,
+    read_status,
     sha256_hex_device,
     sha256_hex_host,
     xor_batch,
@@ -50,5 +51,5 @@ __all__ = [
     "ErrInvalidInput", "decode_rows", "flag_status", "CEC_FLAG_CLEAN", "CEC_FLAG_REBUILT",
     "CEC_FLAG_MANY", "CEC_FLAG_LOST", "CEC_FLAG_MULTI_MAX", "flag_status_multi",
     "confirm_flagged", "confirm_rule", "CEC_CONFIRM_NONE", "CEC_CONFIRM_PROVEN",
-    "CEC_CONFIRM_REFUTED", "CEC_HASHQ_SKIPPED",
+    "CEC_CONFIRM_REFUTED", "CEC_HASHQ_SKIPPED", "read_status",
 ]

@@ -95,6 +95,15 @@ SIGNATURES = {
                                POINTER(c_uint8)]),
     "cec_repair_flagged_multi_ptrs": (c_int, [c_void_p, POINTER(c_void_p), c_void_p, c_size_t,
                                               c_size_t, c_int, c_void_p, c_void_p]),
+    "cec_read_status": (c_int, [c_int, c_int, POINTER(c_uint8), POINTER(c_uint8),
+                                POINTER(c_uint8), c_int, POINTER(c_int), POINTER(c_int),
+                                POINTER(c_uint8)]),
+    "cec_read_solve": (c_int, [c_int, c_int, POINTER(c_uint8), POINTER(c_uint8), POINTER(c_uint8),
+                               c_int, POINTER(c_int), POINTER(c_int), POINTER(c_uint8),
+                               POINTER(c_uint8), POINTER(c_uint8), POINTER(c_uint8),
+                               POINTER(c_int)]),
+    "cec_read_flagged_ptrs": (c_int, [c_void_p, POINTER(c_void_p), c_void_p, POINTER(c_void_p),
+                                      c_size_t, c_size_t, c_int, c_void_p, c_void_p]),
     "cec_encode_idx_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_size_t,
                                      c_size_t, c_int, c_void_p]),
     "cec_update_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,

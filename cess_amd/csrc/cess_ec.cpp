@@ -32,6 +32,7 @@
 #include "fftdec_cost.h"
 #include "fftdec_plan.h"
 #include "flag_solve.h"
+#include "read_plan.h"
 #include "gf256.h"
 #include "hashq_where.h"
 #include "host_util.h"
@@ -2102,6 +2103,165 @@ int cec_repair_flagged_multi_ptrs(cec_codec* c, uint8_t* const* shards, const ui
                                pick_stream(c, hip_stream));
   return repair_flagged_multi_impl(c, shards, d_flags, nseg, shard_len, max_bad, d_status,
                                    pick_stream(c, hip_stream));
+}
+
+// ---- a degraded read decided from flags (read_plan.h) -----------------------------------------
+
+static int check_read_args(int k, int m, const uint8_t* held, const uint8_t* flags,
+                           const uint8_t* wanted, int max_bad) {
+  if (!held || !flags || !wanted) return set_err(CEC_EINVAL, "null");
+  return check_flag_multi(k, m, max_bad);
+}
+
+int cec_read_solve(int k, int m, const uint8_t* held, const uint8_t* flags, const uint8_t* wanted,
+                   int max_bad, int* status, int* nout, uint8_t* out_idx, uint8_t* in_idx,
+                   uint8_t* rows, uint8_t* copy_idx, int* ncopy) {
+  if (!status || !nout || !ncopy) return set_err(CEC_EINVAL, "null");
+  if (int rc = check_read_args(k, m, held, flags, wanted, max_bad)) return rc;
+  uint32_t st = 0, e = 0, nc = 0;
+  cec::rp_plan_segment((uint32_t)k, (uint32_t)(k + m), held, flags, wanted, (uint32_t)max_bad, &st,
+                       &e, out_idx, in_idx, rows, nullptr, copy_idx, &nc, nullptr);
+  *status = (int)st;
+  *nout = (int)e;
+  *ncopy = (int)nc;
+  return CEC_OK;
+}
+
+int cec_read_status(int k, int m, const uint8_t* held, const uint8_t* flags, const uint8_t* wanted,
+                    int max_bad, int* status, int* nmiss, uint8_t* miss) {
+  if (!nmiss) return set_err(CEC_EINVAL, "null");
+  int ncopy = 0;
+  return cec_read_solve(k, m, held, flags, wanted, max_bad, status, nmiss, miss, nullptr, nullptr,
+                        nullptr, &ncopy);
+}
+
+// cec_read_flagged_ptrs: cec_repair_flagged_multi_ptrs aimed at a destination. The host uploads
+// the shard addresses and the destinations and nothing else; the planner (kernels.h ReadPlan)
+// applies the rule, writes the copy rows of every segment and, for a rebuilt one, its program
+// chunk and its product row; the gated copy and one product launch per bucket follow it on `st`.
+// RS(2,1) takes k_ptr21's closed forms and needs no chunk. Nothing here waits for `st` or copies
+// from the device, and the decode cache is not touched.
+static int read_flagged_impl(cec_codec* c, const uint8_t* const* shards, const uint8_t* d_flags,
+                             uint8_t* const* dst, size_t nseg, size_t shard_len, int max_bad,
+                             uint8_t* d_status, hipStream_t st) {
+  const int n = c->k + c->m, k = c->k;
+  const bool ct21 = k == 2 && c->m == 1 && !c->force_generic;
+  if (nseg * (size_t)k > 0xffffffffull) return set_err(CEC_EINVAL, "too many copy rows");
+  // the upload: [nseg][n] shard addresses, then [nseg][k] destinations
+  const size_t dst_at = nseg * n;
+  std::vector<uint64_t> host(dst_at + nseg * k, 0);
+  std::unordered_set<uintptr_t> held, outs;
+  uintptr_t bits = 0;  // OR of every held address and every destination: the call's alignment
+  int most = 0;        // the most shards any segment wants
+  for (size_t i = 0; i < nseg * n; ++i) {
+    if (!shards[i]) continue;
+    held.insert((uintptr_t)shards[i]);
+    bits |= (uintptr_t)shards[i];
+    host[i] = (uint64_t)(uintptr_t)shards[i];
+  }
+  for (size_t s = 0; s < nseg; ++s) {
+    int want = 0;
+    for (int j = 0; j < k; ++j) {
+      uint8_t* const a = dst[s * k + j];
+      if (!a) continue;
+      if (!outs.insert((uintptr_t)a).second)
+        return set_err(CEC_EINVAL, "a destination address is named twice");
+      if (held.count((uintptr_t)a))
+        return set_err(CEC_EINVAL, "a destination is a shard of the call (the repair heals in place)");
+      bits |= (uintptr_t)a;
+      host[dst_at + s * k + j] = (uint64_t)(uintptr_t)a;
+      ++want;
+    }
+    most = std::max(most, want);
+  }
+  const bool vec_ok = (bits & 15) == 0;
+  // a segment rebuilds its missing wanted data shards: at most max_bad, m (k good ones remain) and
+  // what it wants. < 1: nothing is wanted anywhere, every row of the call is idle
+  const int widest = std::min({max_bad, c->m, most});
+  // one pool block: the upload, the copy rows [nseg][k][2], then the product rows: RS(2,1)
+  // [nseg][4], else bucket b's table [nseg][k + 1 + b]
+  const size_t copy_at = host.size();
+  size_t words = copy_at + nseg * (size_t)k * cec::kRpCopyWords;
+  size_t rows_at[CEC_FLAG_MULTI_MAX] = {};
+  if (ct21) {
+    rows_at[0] = words;
+    words += nseg * cec::kRp21RowWords;
+  } else {
+    for (int b = 1; b <= widest; ++b) {
+      rows_at[b - 1] = words;
+      words += nseg * (size_t)cec::rp_row_words((uint32_t)k, (uint32_t)b);
+    }
+  }
+  const size_t bytes = words * sizeof(uint64_t);
+  void* d = nullptr;
+  int rc = c->pool.alloc(bytes, &d);
+  if (rc) return rc;
+  // the segments' chunks: written and read on `st` only, so a large block is stream-ordered
+  const size_t chunk_words =
+      ct21 || widest < 1 ? 0 : cec::fs_chunk_words((uint32_t)k, (uint32_t)widest);
+  Scratch progs;
+  if (chunk_words) rc = scratch_alloc(c, nseg * chunk_words * sizeof(uint32_t), st, &progs);
+  hipError_t e = hipSuccess;
+  if (!rc) {
+    e = hipMemcpyAsync(d, host.data(), host.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
+                       c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess)
+      rc = set_err(CEC_EHIP, std::string("table upload: ") + hipGetErrorString(e));
+  }
+  if (rc) {
+    c->pool.retire(d, bytes);
+    scratch_release(c, progs, st);
+    return rc;
+  }
+  uint64_t* dw = static_cast<uint64_t*>(d);
+  cec::ReadPlan rp{};
+  rp.segs = dw;
+  rp.dst = dw + dst_at;
+  rp.flags = d_flags;
+  rp.status = d_status;
+  rp.copy = dw + copy_at;
+  if (ct21) rp.rows[0] = dw + rows_at[0];
+  else
+    for (int b = 1; b <= widest; ++b) rp.rows[b - 1] = dw + rows_at[b - 1];
+  rp.chunks = static_cast<uint32_t*>(progs.p);
+  rp.chunk_words = (uint32_t)chunk_words;
+  rp.nseg = (uint32_t)nseg;
+  rp.n = n;
+  rp.k = k;
+  rp.max_bad = max_bad;
+  cec::launch_read_plan(rp, ct21, st);
+  rc = check_launch();
+  if (!rc) {
+    cec::launch_read_copy(rp.copy, (uint64_t)nseg * k, shard_len, vec_ok, st);
+    rc = check_launch();
+  }
+  if (!rc && ct21) {
+    cec::launch_ptrs_rs21(cec::PtrSink::store, rp.rows[0], rp.nseg, shard_len, vec_ok, nullptr, st);
+    rc = check_launch();
+  }
+  for (int b = 1; !ct21 && b <= widest && !rc; ++b) {
+    cec::launch_ptrs_rt_flag(cec::rt_takes_rtb(c->opts, b, k), rp.rows[b - 1], rp.nseg,
+                             cec::rp_row_words((uint32_t)k, (uint32_t)b), b, shard_len, vec_ok, st);
+    rc = check_launch();
+  }
+  const int mrc = c->pool.mark(st);  // the tables and the chunks stay until these complete
+  c->pool.retire(d, bytes);
+  scratch_release(c, progs, st);
+  return rc ? rc : mrc;
+}
+
+int cec_read_flagged_ptrs(cec_codec* c, const uint8_t* const* shards, const uint8_t* d_flags,
+                          uint8_t* const* dst, size_t nseg, size_t shard_len, int max_bad,
+                          uint8_t* d_status, void* hip_stream) {
+  if (!c || (nseg && (!shards || !d_flags || !dst || !d_status)))
+    return set_err(CEC_EINVAL, "null");
+  if (int rc = check_flag_multi(c->k, c->m, max_bad)) return rc;
+  if (int rc = check_batch(nseg, shard_len)) return rc;
+  if (nseg == 0) return CEC_OK;
+  CEC_HIP_TRY(hipSetDevice(c->device));
+  return read_flagged_impl(c, shards, d_flags, dst, nseg, shard_len, max_bad, d_status,
+                           pick_stream(c, hip_stream));
 }
 
 int cec_reconstruct_partial_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size_t nseg,

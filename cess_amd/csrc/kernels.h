@@ -208,6 +208,37 @@ struct FlagPlanMulti {
 // Row s and chunk s are segment s's: no atomics, no compaction, the tables of two runs are equal.
 void launch_flag_plan_multi(const FlagPlanMulti& p, hipStream_t st);
 
+// A degraded read decided on the GPU (cec_read_flagged_ptrs, read_plan.h): the wanted data shards
+// of a segment arrive at the caller's destinations, the good ones copied, the missing ones
+// (wanted and not held, or held with flag 0) rebuilt from the first k good shards. The rule is
+// cec_read_status's: nothing missing: clean; fewer than k good: lost; up to max_bad missing:
+// rebuilt; else many. Nothing at `segs` is ever an output.
+struct ReadPlan {
+  const uint64_t* segs;   // [nseg][n]: a segment's n shard addresses (0: not held)
+  const uint64_t* dst;    // [nseg][k]: where data shard j is wanted (0: not wanted)
+  const uint8_t* flags;   // [nseg][n], any alignment; bytes of shards not held are not read
+  uint8_t* status;        // [nseg]: kFlag* per segment
+  uint64_t* copy;         // [nseg][k][2]: {src, dst} of every good wanted data shard of a clean or
+                          // rebuilt segment, {0, 0} elsewhere
+  uint64_t* rows[4];      // any code: rows[b - 1] is the table of bucket b, [nseg][k + 1 + b]
+                          // words (null: no table); RS(2,1): rows[0] is [nseg][4], k_ptr21's rows
+  uint32_t* chunks;       // [nseg][chunk_words]: segment s's program chunk (unused for RS(2,1))
+  uint32_t chunk_words;   // fs_chunk_words(k, the widest bucket with a table)
+  uint32_t nseg;
+  int n, k, max_bad;
+};
+// rs21: one lane per segment, rows {input 0, input 1, destination, case 0 / 1} or the idle {0, 0,
+// 0, 3}. Otherwise one wave per segment: a segment rebuilt with e missing shards gets {its chunk,
+// its first k good shards, the e destinations} in bucket e's table and its chunk written; its row
+// in every other table, and every row of a segment that is not rebuilt, is zero in every word.
+// Rows are written whole with plain stores, row s is segment s's: the tables of two runs are equal.
+void launch_read_plan(const ReadPlan& p, bool rs21, hipStream_t st);
+// The gated copy: `nrows` rows {src, dst}; a workgroup row whose src word is zero leaves after one
+// scalar load, every other streams `len` bytes from src to dst (16-byte columns with a byte tail,
+// or byte-wise for the whole launch without vec_ok).
+void launch_read_copy(const uint64_t* tab, uint64_t nrows, uint64_t len, bool vec_ok,
+                      hipStream_t st);
+
 // SHA-256 of `n` equal-length buffers, written as 64 lowercase hex characters each into
 // `hex_out` (device, n * 64 bytes). If `ptrs` is null, buffer i is shard (i % nshards) of
 // segment (i / nshards) in layout L.

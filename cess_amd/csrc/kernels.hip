@@ -23,6 +23,7 @@
 
 #include "dev_util.h"
 #include "flag_solve.h"
+#include "read_plan.h"
 #include "gf256.h"
 #include "hashq_where.h"
 #include "kernels.h"
@@ -2070,6 +2071,140 @@ __global__ __launch_bounds__(256) void k_flag_plan_multi(FlagPlanMulti p) {
   }
 }
 
+// The planners of a degraded read (kernels.h ReadPlan, read_plan.h): the repair's planners with
+// "missing" counted over the wanted data shards, shards that are not held included, the output
+// addresses taken from the caller's destinations, and the copy rows of the good wanted data shards
+// written beside the product rows. Nothing of `segs` becomes an output.
+
+// RS(2,1): one lane per segment (rp_plan21).
+__global__ __launch_bounds__(256) void k_read_plan21(ReadPlan p) {
+  const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s >= p.nseg) return;
+  const uint64_t* __restrict__ seg = p.segs + s * 3;
+  const uint64_t* __restrict__ dp = p.dst + s * 2;
+  const uint64_t a[3] = {seg[0], seg[1], seg[2]}, d[2] = {dp[0], dp[1]};
+  uint64_t row[kRp21RowWords], cp[2 * kRpCopyWords];
+  p.status[s] = (uint8_t)rp_plan21(a, p.flags + s * 3, d, (uint32_t)p.max_bad, row, cp);
+  uint64_t* __restrict__ ro = p.rows[0] + s * kRp21RowWords;
+  uint64_t* __restrict__ co = p.copy + s * (2 * kRpCopyWords);
+#pragma unroll
+  for (uint32_t t = 0; t < 4; ++t) {
+    ro[t] = row[t];
+    co[t] = cp[t];
+  }
+}
+
+// Any code: k_flag_plan_multi's shape, one wave per segment, four per workgroup, the lanes
+// striding over n for the ballots (counts, the first k good indices in LDS, the first four missing
+// ones in a word), then over k for the copy rows, and for a rebuilt segment over the k survivors.
+__global__ __launch_bounds__(256) void k_read_plan(ReadPlan p) {
+  __shared__ uint8_t surv_all[4][256];
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t s = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= p.nseg) return;  // the whole wave
+  uint8_t* surv = surv_all[threadIdx.x >> 6];
+  const uint32_t n = (uint32_t)p.n, k = (uint32_t)p.k;
+  const uint64_t* __restrict__ seg = p.segs + s * n;
+  const uint64_t* __restrict__ dp = p.dst + s * k;
+  const uint8_t* __restrict__ fl = p.flags + s * n;
+  uint32_t nmiss = 0, ngood = 0, lost = 0;
+  for (uint32_t base = 0; base < n; base += 64) {
+    const uint32_t i = base + lane;
+    const bool held = i < n && seg[i] != 0;
+    const bool good = rp_good(held, held ? fl[i] : 0);
+    const bool wanted = i < k && dp[i] != 0;
+    unsigned long long miss = __ballot(rp_missing(wanted, good));
+    const unsigned long long gm = __ballot(good);
+    const uint32_t pos = ngood + (uint32_t)__popcll(gm & ((1ull << lane) - 1));
+    if (good && pos < k) surv[pos] = (uint8_t)i;
+    ngood += (uint32_t)__popcll(gm);
+    for (; miss; miss &= miss - 1) {
+      if (nmiss < 4) lost |= (base + (uint32_t)__ffsll(miss) - 1) << (8 * nmiss);
+      ++nmiss;
+    }
+  }
+  const uint32_t st = rp_status(nmiss, ngood, k, (uint32_t)p.max_bad);
+  const uint32_t e = st == kFlagRebuilt ? nmiss : 0;
+  if (lane == 0) p.status[s] = (uint8_t)st;
+  // the copy rows: data shard j, wanted and good, of a segment that is read
+  uint64_t* __restrict__ cp = p.copy + s * k * kRpCopyWords;
+  const bool copies = rp_copies(st);
+  for (uint32_t j = lane; j < k; j += 64) {
+    const uint64_t a = seg[j], d = dp[j];
+    rp_put_copy(cp, j, copies && d != 0 && rp_good(a != 0, a ? fl[j] : 0), a, d);
+  }
+  uint64_t* row = nullptr;  // the segment's row in bucket e's table
+#pragma unroll
+  for (uint32_t b = 1; b <= 4; ++b) {
+    uint64_t* const rb = p.rows[b - 1] ? p.rows[b - 1] + s * rp_row_words(k, b) : nullptr;
+    if (b == e) row = rb;
+    else if (rb) rp_put_idle(rb, rp_row_words(k, b), lane, 64);
+  }
+  if (!row) return;  // no rebuild (a rebuilt segment's bucket always has a table)
+  // the survivor list is complete: LDS accesses of one wave complete in order
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  uint32_t* __restrict__ chunk = p.chunks + s * p.chunk_words;
+  uint32_t nj[4];
+#pragma unroll
+  for (uint32_t o = 0; o < 4; ++o) nj[o] = o < e ? fs_numer(surv, k, (lost >> (8 * o)) & 0xFFu) : 0;
+  if (lane == 0) {
+    fs_put_header(chunk, k, e);
+    rp_put_chunk(row, (uint64_t)(uintptr_t)chunk);
+#pragma unroll
+    for (uint32_t o = 0; o < 4; ++o)
+      if (o < e) rp_put_out(row, k, o, dp[(lost >> (8 * o)) & 0xFFu]);
+  }
+  for (uint32_t t = lane; t < k; t += 64) {
+    const uint32_t sv = surv[t];
+    rp_put_in(row, t, seg[sv]);
+    const uint32_t dt = fs_denom(surv, k, t);
+    uint32_t col = 0;
+#pragma unroll
+    for (uint32_t o = 0; o < 4; ++o)
+      if (o < e) col |= fs_coef(nj[o], (lost >> (8 * o)) & 0xFFu, sv, dt) << (8 * o);
+    fs_put_column(chunk, e, t, col);
+  }
+}
+
+// The gated copy of a read: row = {src, dst} in one scalar load, a zero src ends the workgroup
+// there. U 16-byte columns per lane, all loads issued before the first store, with the streamed
+// (non-temporal) forms k_ptr21 takes for RS(2,1)'s columns; then the byte tail in the last block,
+// or the whole shard byte-wise.
+constexpr int kReadCopyU = 4;
+template <int U>
+__global__ __launch_bounds__(256) void k_read_copy(const uint64_t* __restrict__ tab, uint32_t row0,
+                                                   uint64_t len, int vec_ok) {
+  const cu64* __restrict__ row = tab_row(tab, row0 + blockIdx.y, kRpCopyWords);
+  const uint64_t sa = row[0], da = row[1];
+  if (sa == 0) return;
+  gu8* const src = gptr(sa);
+  gu8* const dst = gptr(da);
+  using TV = u32x4;
+  constexpr int VB = sizeof(TV);
+  if (vec_ok) {
+    const uint64_t nvec = len / VB;
+    const uint64_t base = (uint64_t)blockIdx.x * (256 * U) + threadIdx.x;
+    TV x[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint64_t v = base + u * 256;
+      x[u] = v < nvec ? gld<true, TV>(src + v * VB) : TV(0);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint64_t v = base + u * 256;
+      if (v < nvec) gst<true, TV>(dst + v * VB, x[u]);
+    }
+    if (!(len % VB) || blockIdx.x != gridDim.x - 1) return;
+  }
+  // byte path: whole shard (vec_ok == 0, grid covers len) or the tail (last block)
+  const uint64_t i = vec_ok ? (len - len % VB) + threadIdx.x
+                            : (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= len) return;
+  dst[i] = src[i];
+}
+
 namespace {
 // A launch's sink as a type: f(SinkTag<Sink>, the sink's kernel arguments...).
 template <class Sink>
@@ -2151,6 +2286,26 @@ void launch_flag_plan_multi(const FlagPlanMulti& p, hipStream_t st) {
   if (p.nseg == 0) return;
   hipLaunchKernelGGL(k_flag_plan_multi, dim3((unsigned)(((uint64_t)p.nseg + 3) / 4)), dim3(256), 0,
                      st, p);
+}
+
+void launch_read_plan(const ReadPlan& p, bool rs21, hipStream_t st) {
+  if (p.nseg == 0) return;
+  if (rs21)
+    hipLaunchKernelGGL(k_read_plan21, dim3((unsigned)(((uint64_t)p.nseg + 255) / 256)), dim3(256), 0,
+                       st, p);
+  else
+    hipLaunchKernelGGL(k_read_plan, dim3((unsigned)(((uint64_t)p.nseg + 3) / 4)), dim3(256), 0,
+                       st, p);
+}
+
+void launch_read_copy(const uint64_t* tab, uint64_t nrows, uint64_t len, bool vec_ok,
+                      hipStream_t st) {
+  const unsigned gx = rt_grid_x(len, 16, kReadCopyU, vec_ok);
+  const int v = vec_ok ? 1 : 0;
+  // the chunks are a whole number of rows each: the kernel's row index stays 32-bit per chunk
+  for_y_chunks(nrows, [&](uint32_t r0, uint32_t ny) {
+    hipLaunchKernelGGL(k_read_copy<kReadCopyU>, dim3(gx, ny), dim3(256), 0, st, tab, r0, len, v);
+  });
 }
 
 // cec_confirm_flagged: what the checked chains of the rebuilt fragments proved, per segment. One

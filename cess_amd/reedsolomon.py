@@ -543,6 +543,86 @@ class Encoder:
         check(rc, what)
         return d_status
 
+    def ReadFlaggedDevice(self, segments: Sequence, d_flags, out,
+                          max_bad: int = _lib.CEC_FLAG_MULTI_MAX, wanted=None, d_status=None,
+                          stream=None):
+        """A verified degraded read decided on the GPU (cec_read_flagged_ptrs): `segments` and
+        `d_flags` as in RepairFlaggedMultiDevice, but the shards are only read. `out` receives the
+        data: a uint8 device tensor [nseg, k*F] whose row s is segment s's joined data (data
+        shard j at columns j*F..), with `wanted` an optional [nseg][k] mask of the shards to
+        deliver (default: all); or a list of nseg*k 1-D tensors of F bytes / None (None = not
+        wanted), segment-major. Per segment: nothing wanted missing: every wanted shard is copied
+        (CLEAN); fewer than k good: nothing written (LOST); up to `max_bad` wanted data shards
+        not held or flagged bad: the good wanted ones are copied and the missing ones rebuilt into
+        `out` from the first k good shards (REBUILT); else nothing written (MANY). read_status
+        states the rule. Returns the uint8 device tensor of len(segments) CEC_FLAG_* codes,
+        `d_status` if given. Every tensor must be contiguous and on the codec's GPU; an `out`
+        tensor that is a shard of the call, or named twice, is refused (ErrInvalidInput).
+        Enqueued on `stream` (default: torch's current stream) and not waited for, and no flag is
+        copied to the host."""
+        import torch
+        if not 1 <= int(max_bad) <= _lib.CEC_FLAG_MULTI_MAX:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        nseg, n, k = len(segments), self.Shards, self.DataShards
+        dev = torch.device("cuda", self.device)
+        if (d_flags.dtype != torch.uint8 or d_flags.numel() != nseg * n or d_flags.device != dev
+                or not d_flags.is_contiguous()):
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        if d_status is None:
+            d_status = torch.empty(nseg, dtype=torch.uint8, device=dev)
+        elif (d_status.dtype != torch.uint8 or d_status.dim() != 1 or d_status.numel() != nseg
+              or d_status.device != dev or not d_status.is_contiguous()):
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        if nseg == 0:
+            return d_status
+        if self.ParityShards == 0:  # no parity, no codec: a plain copy is the caller's
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        ptrs = (c_void_p * (nseg * n))()
+        held = []
+        for s, shards in enumerate(segments):
+            if len(shards) != n:
+                raise ErrTooFewShards(ErrTooFewShards.__doc__)
+            for i, t in enumerate(shards):
+                if t is None:
+                    continue
+                held.append(_on_gpu(t, dev))
+                ptrs[s * n + i] = _dev_ptr(t)
+        dst = (c_void_p * (nseg * k))()
+        if isinstance(out, torch.Tensor):
+            if (out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != nseg
+                    or out.shape[1] % k or out.shape[1] == 0 or out.device != dev
+                    or not out.is_contiguous()):
+                raise ErrInvalidInput(ErrInvalidInput.__doc__)
+            size = out.shape[1] // k
+            if wanted is not None and (len(wanted) != nseg or any(len(w) != k for w in wanted)):
+                raise ErrInvalidInput(ErrInvalidInput.__doc__)
+            base = _dev_ptr(out)
+            for s in range(nseg):
+                for j in range(k):
+                    if wanted is None or wanted[s][j]:
+                        dst[s * k + j] = base + (s * k + j) * size
+            if held and self._check_device_shards(held) != size:
+                raise ErrShardSize(ErrShardSize.__doc__)
+        else:
+            if wanted is not None or len(out) != nseg * k:
+                raise ErrInvalidInput(ErrInvalidInput.__doc__)
+            outs = []
+            for i, t in enumerate(out):
+                if t is None:
+                    continue
+                outs.append(_on_gpu(t, dev))
+                dst[i] = _dev_ptr(t)
+            # one length over the shards and the destinations together
+            size = self._check_device_shards(held + outs) if held or outs else 1
+        rc = self._lib.cec_read_flagged_ptrs(self._h, ptrs, _dev_ptr(d_flags), dst, nseg, size,
+                                             int(max_bad), _dev_ptr(d_status),
+                                             self._device_stream(stream))
+        if rc == _lib.CEC_EINVAL:  # a destination named twice, or one that is a shard of the call
+            detail = self._lib.cec_last_error().decode()
+            raise ErrInvalidInput(f"ReadFlaggedDevice: {detail}")
+        check(rc, "ReadFlaggedDevice")
+        return d_status
+
     def ReconstructPartialDevice(self, shards: Sequence, present, out=None,
                                  accumulate: bool = False, stream=None) -> dict:
         """Partial rebuild of one segment in place (cec_reconstruct_partial_ptrs). `shards` is a
@@ -962,6 +1042,27 @@ def flag_status_multi(data_shards: int, parity_shards: int, held, flags, max_bad
                                             f.ctypes.data_as(u8p), max_bad, byref(status),
                                             byref(nlost), lost), "flag_status_multi")
     return status.value, [int(x) for x in lost[:nlost.value]]
+
+
+def read_status(data_shards: int, parity_shards: int, held, flags, wanted, max_bad: int):
+    """Host only (cec_read_status): the rule ReadFlaggedDevice applies to one segment on the GPU.
+    `held` and `flags` are k+m values each (a held shard whose flag is not 0 is good), `wanted` k
+    values naming the data shards to deliver. A wanted data shard that is not good is missing.
+    Returns (CEC_FLAG_* status, the ascending list of the shards a REBUILT segment rebuilds into
+    its destination, empty for every other status)."""
+    n = data_shards + parity_shards
+    h = np.ascontiguousarray(np.asarray(held, dtype=np.uint8))
+    f = np.ascontiguousarray(np.asarray(flags, dtype=np.uint8))
+    w = np.ascontiguousarray(np.asarray(wanted, dtype=np.uint8))
+    if h.shape != (n,) or f.shape != (n,) or w.shape != (data_shards,):
+        raise ValueError("held and flags must have k+m values, wanted k")
+    status, nmiss = c_int(-1), c_int(0)
+    miss = (c_uint8 * _lib.CEC_FLAG_MULTI_MAX)()
+    u8p = POINTER(c_uint8)
+    check(_lib.load().cec_read_status(data_shards, parity_shards, h.ctypes.data_as(u8p),
+                                      f.ctypes.data_as(u8p), w.ctypes.data_as(u8p), max_bad,
+                                      byref(status), byref(nmiss), miss), "read_status")
+    return status.value, [int(x) for x in miss[:nmiss.value]]
 
 
 def confirm_rule(status: int, ok) -> int:

@@ -295,3 +295,64 @@ def retrieve_file(rec: FileRecord, fetch: FetchFn, out: Union[str, BinaryIO],
     """One-shot Retriever(...).retrieve(rec, fetch, out)."""
     with Retriever(k, m, segment_size, device, **kw) as r:
         return r.retrieve(rec, fetch, out)
+
+
+def read_segments_device(enc, segments, recorded, seg_recorded=None, out=None, max_bad: int = 1,
+                         queue=None):
+    """The degraded read for fragments that already lie in HBM (a gateway's cache, a rank that
+    received them over the fabric), decided on the GPU: `segments` is a list of lists of k + m
+    1-D uint8 device tensors of one length F (None = not held), `recorded` their hashes as in
+    audit.scrub_repair_device, `seg_recorded` optionally the recorded segment hashes (a list of
+    nseg 64-byte `bytes`, or a device / pinned uint8 tensor [nseg][64]). All on `queue`'s stream,
+    nothing waited for or copied out:
+
+      * every held fragment gets a checked chain (HashQueue.add_check_ptrs, flags segment-major),
+        ticked to completion;
+      * Encoder.ReadFlaggedDevice reads the flags where the ticks left them: row s of `out`
+        ([nseg, k*F] uint8, allocated when None) receives segment s's k data fragments, joined,
+        the good ones copied and up to `max_bad` missing ones rebuilt from the good; the fragments
+        themselves are not written;
+      * with `seg_recorded`, one checked chain of k*F bytes per row of `out` against the recorded
+        segment hash (HashQueue.add_check), ticked to completion.
+
+    Returns (out, d_flags [nseg][k + m], d_status [nseg] of CEC_FLAG_* codes, d_seg_ok [nseg] or
+    None), all final when the stream gets there. Rows of LOST and MANY segments are not written,
+    and their d_seg_ok says what the bytes left there hash to. A caller's queue has to be idle and
+    hold the held fragments' chains (and nseg); queue None: a queue of the call's size on torch's
+    current stream, owned and closed by the call."""
+    import torch
+    from .audit import _scrub_table
+    from .hashq import HashQueue
+    from .reedsolomon import ErrInvalidInput
+    segments, slots, rec, runs, d_flags = _scrub_table(enc, segments, recorded)
+    nseg, k = len(segments), enc.DataShards
+    dev = torch.device("cuda", enc.device)
+    sizes = {t.numel() for t in slots if t is not None}
+    if out is None:
+        if len(sizes) != 1:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        out = torch.empty((nseg, k * sizes.pop()), dtype=torch.uint8, device=dev)
+
+    def go(q):
+        stream = q.stream if q.stream is not None else 0  # a queue without one: the null stream
+        flat = d_flags.view(-1)
+        for a, b in runs:
+            q.add_check_ptrs(slots[a:b], rec[a:b], flat[a:b])
+        q.finish()
+        d_status = enc.ReadFlaggedDevice(segments, d_flags, out, max_bad=max_bad, stream=stream)
+        d_seg_ok = None
+        if seg_recorded is not None and nseg:
+            d_seg_ok = torch.empty(nseg, dtype=torch.uint8, device=dev)
+            exp, up = q._expect(seg_recorded, nseg)
+            ticket = q.add_check(out, nseg, 1, out.shape[1], 0, out.shape[1], exp, 1, d_seg_ok, 1)
+            if up is not None:
+                q._kept.append((ticket, up))
+            q.finish()
+        return out, d_flags, d_status, d_seg_ok
+
+    if queue is not None:
+        return go(queue)
+    held = sum(b - a for a, b in runs)
+    cap = 1 << max(0, max(held, nseg) - 1).bit_length()
+    with HashQueue(capacity=cap, device=enc.device, stream=torch.cuda.current_stream(dev)) as q:
+        return go(q)

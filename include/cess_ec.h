@@ -382,6 +382,73 @@ int cec_flag_solve(int k, int m, const uint8_t* held, const uint8_t* flags, int 
 int cec_repair_flagged_multi_ptrs(cec_codec* codec, uint8_t* const* shards, const uint8_t* d_flags,
                                   size_t nseg, size_t shard_len, int max_bad, uint8_t* d_status,
                                   void* hip_stream);
+/* A degraded read decided from the same flags: the wanted data shards of every segment arrive,
+ * verified, in the caller's own buffers (klauspost ReconstructData + Join); the good ones are
+ * copied, the missing ones rebuilt into the destination. Nothing is healed: the shards are
+ * read-only, and a shard that is absent can be read around. No status value is added; the four
+ * codes mean, per segment: CLEAN every wanted shard copied, REBUILT good wanted shards copied and
+ * the missing ones rebuilt, MANY and LOST no destination byte written.
+ * Host only: the rule. held, flags: k+m bytes each, wanted: k bytes. good = held and flag != 0,
+ * over all k+m shards (flags of shards not held are ignored). A wanted data shard is missing when
+ * it is not good (not held, or held with flag 0); miss = their count. miss == 0: CEC_FLAG_CLEAN.
+ * good < k: CEC_FLAG_LOST. miss <= max_bad: CEC_FLAG_REBUILT; *nmiss receives miss and
+ * miss_idx[0 .. *nmiss) (CEC_FLAG_MULTI_MAX bytes, may be NULL) the missing shards, ascending.
+ * Otherwise CEC_FLAG_MANY. *nmiss is 0 and miss_idx is not written for every status but REBUILT.
+ * Bad or absent parity is simply not good; a data shard that is not wanted never counts as
+ * missing. max_bad must be in [1, CEC_FLAG_MULTI_MAX] (CEC_EINVAL). */
+int cec_read_status(int k, int m, const uint8_t* held, const uint8_t* flags, const uint8_t* wanted,
+                    int max_bad, int* status, int* nmiss, uint8_t* miss_idx);
+/* Host only: what the device computes for one segment. Status and *nout as above; for a REBUILT
+ * segment out_idx (CEC_FLAG_MULTI_MAX bytes), in_idx (k bytes, the first k good shards in index
+ * order) and rows (CEC_FLAG_MULTI_MAX * k bytes) are as in cec_flag_solve, the outputs being the
+ * missing shards. copy_idx[0 .. *ncopy) (k bytes, may be NULL) are the data shards that are copied,
+ * ascending: the wanted good ones of a CLEAN or REBUILT segment, none (*ncopy == 0) of a LOST or
+ * MANY one. out_idx, in_idx and rows may each be NULL. The function runs the planner kernel's own
+ * pieces (csrc/read_plan.h over csrc/flag_solve.h) with loops in place of lanes. */
+int cec_read_solve(int k, int m, const uint8_t* held, const uint8_t* flags, const uint8_t* wanted,
+                   int max_bad, int* status, int* nout, uint8_t* out_idx, uint8_t* in_idx,
+                   uint8_t* rows, uint8_t* copy_idx, int* ncopy);
+/* The read. shards, d_flags, d_status, nseg and shard_len as in cec_repair_flagged_multi_ptrs
+ * (shards: HOST array of nseg*n DEVICE pointers, NULL = not held; d_flags: nseg*n DEVICE bytes at
+ * any alignment; d_status: nseg DEVICE bytes), but shards is read-only here. dst is a HOST array
+ * of nseg*k DEVICE pointers: dst[s*k+j] non-NULL = data shard j of segment s is wanted at that
+ * address (shard_len bytes), NULL = not wanted: neither copied nor rebuilt, and never counted as
+ * missing. d_status[s] follows cec_read_status. Parity is never an output.
+ *  - Reads: d_flags (bytes of shards not held are not looked at); of a CLEAN segment its good
+ *    wanted data shards; of a REBUILT segment its first k good shards in index order only (every
+ *    good data shard is among them). Shards flagged bad, good shards past the first k, and every
+ *    shard of a LOST or MANY segment are not read.
+ *  - Writes: d_status, and shard_len bytes at each wanted dst of CLEAN and REBUILT segments.
+ *    Nothing else: not shards, not d_flags, no dst of a LOST or MANY segment.
+ *  - Not waited for: everything that depends on the flags is enqueued on hip_stream and the call
+ *    returns; the flags may still be in production by work queued earlier on that stream. No
+ *    stream synchronise, no device-to-host copy. (It waits for the codec's own upload stream, for
+ *    its table, as the other _ptrs calls do.)
+ *  - Validation: before anything is enqueued; on an error no byte is written. CEC_EINVAL: a NULL
+ *    codec; max_bad outside [1, CEC_FLAG_MULTI_MAX]; with nseg > 0 a NULL shards, d_flags, dst or
+ *    d_status; the same non-NULL dst address twice; a dst address equal to any shard address of
+ *    the call (healing in place is the repair calls' job; equal addresses are what is checked).
+ *    CEC_ESHARDLEN: shard_len == 0. nseg == 0: CEC_OK. A segment with no wanted shard is CLEAN and
+ *    costs one idle row.
+ *  - Alignment: any; 16-byte columns with a byte tail when every held address and every dst is
+ *    16-byte aligned, otherwise the whole call runs byte-wise.
+ *  - Memory: the tables (8n + 8k bytes of addresses, 16k of copy rows and 8(k+1+b) per bucket b of
+ *    product rows per segment) come from the codec's pool and are retired behind the launches:
+ *    CEC_STAT_POOL_BYTES does not grow across repeated calls. The program chunks, 4(772 + 8ke)
+ *    bytes per segment with e the widest bucket, are one block as in the multi repair: a pool
+ *    block below 16 MiB, stream-ordered scratch on hip_stream from there on. The decode cache is
+ *    neither read nor filled (CEC_STAT_DECODE_CACHED does not change). Not capturable into a HIP
+ *    graph, for the reasons given at cec_reconstruct_ptrs.
+ * A planner kernel applies the rule, writes k copy rows {src, dst} per segment and, for a REBUILT
+ * segment, solves its rows and writes its chunk and its product row; a gated copy kernel runs over
+ * the nseg*k copy rows; then one launch of the table-addressed product per bucket b <= min(max_bad,
+ * m, the most shards a segment wants), each over all nseg rows. An idle row costs one row of
+ * workgroups that leave after one scalar load. RS(2,1) without CEC_OPT_FORCE_GENERIC takes its
+ * closed forms and needs no chunk. In a REBUILT segment the good wanted data shards are read
+ * twice, once by the copy and once by the product. */
+int cec_read_flagged_ptrs(cec_codec* codec, const uint8_t* const* shards, const uint8_t* d_flags,
+                          uint8_t* const* dst, size_t nseg, size_t shard_len, int max_bad,
+                          uint8_t* d_status, void* hip_stream);
 /* What a repair proved, per segment: the close of restoral_order_complete, which the chain accepts
  * only if the regenerated fragment hashes to its recorded fragment_hash. After the repairs above,
  * cec_hashq_add_check_where_ptrs (cess_ec.h below) re-hashes exactly the rebuilt fragments; this

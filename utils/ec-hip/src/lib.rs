@@ -200,6 +200,17 @@ pub mod sys {
                                              d_flags: *const u8, nseg: usize, shard_len: usize,
                                              max_bad: c_int, d_status: *mut u8,
                                              stream: *mut c_void) -> c_int;
+        pub fn cec_read_status(k: c_int, m: c_int, held: *const u8, flags: *const u8,
+                               wanted: *const u8, max_bad: c_int, status: *mut c_int,
+                               nmiss: *mut c_int, miss_idx: *mut u8) -> c_int;
+        pub fn cec_read_solve(k: c_int, m: c_int, held: *const u8, flags: *const u8,
+                              wanted: *const u8, max_bad: c_int, status: *mut c_int,
+                              nout: *mut c_int, out_idx: *mut u8, in_idx: *mut u8, rows: *mut u8,
+                              copy_idx: *mut u8, ncopy: *mut c_int) -> c_int;
+        pub fn cec_read_flagged_ptrs(c: *mut cec_codec, shards: *const *const u8,
+                                     d_flags: *const u8, dst: *const *mut u8, nseg: usize,
+                                     shard_len: usize, max_bad: c_int, d_status: *mut u8,
+                                     stream: *mut c_void) -> c_int;
         pub fn cec_encode_idx_batch(c: *mut cec_codec, d_shard: *const u8,
                                     shard_seg_stride: usize, idx: c_int, d_parity: *mut u8,
                                     nseg: usize, shard_len: usize, accumulate: c_int,
@@ -752,6 +763,53 @@ impl ReedSolomon {
                                   max_bad as c_int, &mut status, &mut nlost, lost.as_mut_ptr())
         })?;
         Ok((status, lost[..nlost as usize].iter().map(|&i| i as usize).collect()))
+    }
+
+    /// A verified degraded read decided on the GPU (`cec_read_flagged_ptrs`): `shards` and
+    /// `d_flags` as in `repair_flagged_multi_ptrs`, but the shards are only read. `dst` holds
+    /// `nseg * k` device addresses, segment by segment: a non-null entry is where that data shard
+    /// is wanted (`shard_len` bytes), null means not wanted. Per segment the good wanted data
+    /// shards are copied and up to `max_bad` missing ones (not held, or flagged bad) rebuilt into
+    /// their destinations from the first k good shards; `d_status` receives one `CEC_FLAG_*` code
+    /// per segment (`read_status` states the rule), and no destination of a `CEC_FLAG_LOST` or
+    /// `CEC_FLAG_MANY` segment is written. Enqueued on `stream` and not waited for; no flag is
+    /// copied to the host.
+    ///
+    /// # Safety
+    /// Every non-null entry of `shards` and `dst` must be valid device memory of `shard_len`
+    /// bytes, `d_flags` of `shards.len()` bytes and `d_status` of one byte per segment, all until
+    /// the work enqueued on `stream` has run; no destination may overlap a shard or another
+    /// destination.
+    pub unsafe fn read_flagged_ptrs(&self, shards: &[*const u8], d_flags: *const u8,
+                                    dst: &[*mut u8], shard_len: usize, max_bad: i32,
+                                    d_status: *mut u8, stream: *mut c_void) -> Result<(), Error> {
+        let n = self.k + self.m;
+        if shards.len() % n != 0 || dst.len() != shards.len() / n * self.k {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        check(cec_read_flagged_ptrs(self.c, shards.as_ptr(), d_flags, dst.as_ptr(),
+                                    shards.len() / n, shard_len, max_bad as c_int, d_status,
+                                    stream))
+    }
+
+    /// The rule `read_flagged_ptrs` applies to one segment (`cec_read_status`, host only):
+    /// `wanted` names the k data shards to deliver. Returns the `CEC_FLAG_*` status and the
+    /// ascending indices of the data shards a `CEC_FLAG_REBUILT` segment rebuilds into its
+    /// destinations (empty for every other status).
+    pub fn read_status(&self, held: &[u8], flags: &[u8], wanted: &[u8],
+                       max_bad: i32) -> Result<(i32, Vec<usize>), Error> {
+        let n = self.k + self.m;
+        if held.len() != n || flags.len() != n || wanted.len() != self.k {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        let (mut status, mut nmiss): (c_int, c_int) = (0, 0);
+        let mut miss = [0u8; CEC_FLAG_MULTI_MAX as usize];
+        check(unsafe {
+            cec_read_status(self.k as c_int, self.m as c_int, held.as_ptr(), flags.as_ptr(),
+                            wanted.as_ptr(), max_bad as c_int, &mut status, &mut nmiss,
+                            miss.as_mut_ptr())
+        })?;
+        Ok((status, miss[..nmiss as usize].iter().map(|&i| i as usize).collect()))
     }
 
     /// EncodeIdx on scattered device shards in place (`cec_encode_idx_ptrs`): `data` holds
