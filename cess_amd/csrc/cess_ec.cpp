@@ -1853,6 +1853,21 @@ int cec_flag_status(int k, int m, const uint8_t* held, const uint8_t* flags, int
   return CEC_OK;
 }
 
+// The calls that decide on the GPU keep their tables in one pool block. `words` of `host` go to
+// its front on c->stream, which is synchronised: the one host wait of such a call, never on `st`.
+static int upload_table(cec_codec* c, void* d, const uint64_t* host, size_t words) {
+  hipError_t e = hipMemcpyAsync(d, host, words * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) return CEC_OK;
+  return set_err(CEC_EHIP, std::string("table upload: ") + hipGetErrorString(e));
+}
+// Behind the call's launches: the block stays until what is queued on `st` completes.
+static int retire_behind(cec_codec* c, void* d, size_t bytes, hipStream_t st, int rc) {
+  const int mrc = c->pool.mark(st);
+  c->pool.retire(d, bytes);
+  return rc ? rc : mrc;
+}
+
 // cec_repair_flagged_ptrs: which shard of a segment is rebuilt is decided on the device, from
 // flags that may not exist yet when this returns, so the host prepares every answer. Segments are
 // grouped by held set; for a group that holds more than k shards, every held shard j gets the
@@ -1929,16 +1944,14 @@ static int repair_flagged_impl(cec_codec* c, uint8_t* const* shards, const uint8
       std::memcpy(surv + (g * n + j) * k, p->in_idx, k);
     }
   void* d = nullptr;
-  const size_t in_bytes = in_words * sizeof(uint64_t);
-  const size_t bytes = in_bytes + nseg * rs * sizeof(uint64_t);
+  const size_t bytes = (in_words + nseg * rs) * sizeof(uint64_t);
   int rc = c->pool.alloc(bytes, &d);
   if (rc) return rc;
-  hipError_t e = hipMemcpyAsync(d, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the programs' uploads too
+  rc = upload_table(c, d, host.data(), in_words);  // the programs' uploads too
   up.arena.reset();
-  if (e != hipSuccess) {
+  if (rc) {
     c->pool.retire(d, bytes);
-    return set_err(CEC_EHIP, std::string("table upload: ") + hipGetErrorString(e));
+    return rc;
   }
   uint64_t* dw = static_cast<uint64_t*>(d);
   cec::FlagPlan fp{};
@@ -1961,10 +1974,9 @@ static int repair_flagged_impl(cec_codec* c, uint8_t* const* shards, const uint8
                              vec_ok, st);
     rc = check_launch();
   }
-  const int mrc = c->pool.mark(st);  // the table and the programs stay until these complete
-  c->pool.retire(d, bytes);
+  rc = retire_behind(c, d, bytes, st, rc);  // the table and the programs
   evict_decode(c);  // `groups` holds the call's programs to the end
-  return rc ? rc : mrc;
+  return rc;
 }
 
 int cec_repair_flagged_ptrs(cec_codec* c, uint8_t* const* shards, const uint8_t* d_flags,
@@ -2008,12 +2020,65 @@ int cec_flag_status_multi(int k, int m, const uint8_t* held, const uint8_t* flag
   return cec_flag_solve(k, m, held, flags, max_bad, status, nlost, lost, nullptr, nullptr);
 }
 
+// What cec_repair_flagged_multi_ptrs and cec_read_flagged_ptrs do once the caller has scanned its
+// addresses into `host` (the [nseg][n] shard addresses first) and filled what it knows of `fp`.
+// One pool block: the upload, `mid_words` words of the caller's (the read's copy rows), then the
+// product rows: bucket b's table [nseg][k + 1 + b] for b <= widest, or with `ct21` RS(2,1)'s
+// [nseg][4]. The segments' chunks are scratch on `st`. plan(fp, mid) launches the planner, and
+// what else comes before the products, over the completed plan and returns a status; one product
+// launch per table follows it. Nothing here waits for `st` or copies from the device, and the
+// decode cache is not touched.
+extern "C++" template <class Plan>
+static int run_flag_plan(cec_codec* c, const std::vector<uint64_t>& host, size_t mid_words,
+                         bool ct21, int widest, cec::FlagPlanMulti fp, size_t shard_len,
+                         bool vec_ok, hipStream_t st, Plan plan) {
+  const uint32_t k = (uint32_t)fp.k;
+  const size_t nseg = fp.nseg;
+  const int tables = ct21 ? 1 : widest;  // < 1: every row of the call is idle
+  size_t words = host.size() + mid_words, rows_at[CEC_FLAG_MULTI_MAX] = {};
+  for (int b = 1; b <= tables; ++b) {
+    rows_at[b - 1] = words;
+    words += nseg * (ct21 ? cec::kRp21RowWords : cec::fs_row_words(k, (uint32_t)b));
+  }
+  const size_t bytes = words * sizeof(uint64_t);
+  void* d = nullptr;
+  int rc = c->pool.alloc(bytes, &d);
+  if (rc) return rc;
+  // the segments' chunks: written and read on `st` only, so a large block is stream-ordered
+  const size_t chunk_words = ct21 || widest < 1 ? 0 : cec::fs_chunk_words(k, (uint32_t)widest);
+  Scratch progs;
+  if (chunk_words) rc = scratch_alloc(c, nseg * chunk_words * sizeof(uint32_t), st, &progs);
+  if (!rc) rc = upload_table(c, d, host.data(), host.size());
+  if (rc) {
+    c->pool.retire(d, bytes);
+    scratch_release(c, progs, st);
+    return rc;
+  }
+  uint64_t* dw = static_cast<uint64_t*>(d);
+  fp.segs = dw;
+  for (int b = 1; b <= tables; ++b) fp.rows[b - 1] = dw + rows_at[b - 1];
+  fp.chunks = static_cast<uint32_t*>(progs.p);
+  fp.chunk_words = (uint32_t)chunk_words;
+  rc = plan(fp, dw + host.size());
+  if (!rc && ct21) {
+    cec::launch_ptrs_rs21(cec::PtrSink::store, fp.rows[0], fp.nseg, shard_len, vec_ok, nullptr, st);
+    rc = check_launch();
+  }
+  for (int b = 1; !ct21 && b <= widest && !rc; ++b) {
+    cec::launch_ptrs_rt_flag(cec::rt_takes_rtb(c->opts, b, (int)k), fp.rows[b - 1], fp.nseg,
+                             cec::fs_row_words(k, (uint32_t)b), b, shard_len, vec_ok, st);
+    rc = check_launch();
+  }
+  rc = retire_behind(c, d, bytes, st, rc);  // the tables; the chunks stay as long
+  scratch_release(c, progs, st);
+  return rc;
+}
+
 // cec_repair_flagged_multi_ptrs: nothing about a segment is known on the host but what it holds,
 // so the host uploads the addresses and nothing else; the planner kernel (kernels.h
 // FlagPlanMulti) solves every rebuilt segment's rows and writes its program chunk and its table
 // row. One table per bucket b <= max_bad that some held set of the call can fill (k + b shards
-// held), one product launch over all of it behind the planner. Nothing here waits for `st` or
-// copies from the device, and the decode cache is not touched.
+// held), one product launch over all of it behind the planner (run_flag_plan).
 static int repair_flagged_multi_impl(cec_codec* c, uint8_t* const* shards, const uint8_t* d_flags,
                                      size_t nseg, size_t shard_len, int max_bad,
                                      uint8_t* d_status, hipStream_t st) {
@@ -2035,58 +2100,18 @@ static int repair_flagged_multi_impl(cec_codec* c, uint8_t* const* shards, const
     }
     most = std::max(most, nheld);
   }
-  const bool vec_ok = (bits & 15) == 0;
-  const int widest = std::min({max_bad, c->m, most - k});  // < 1: every row of the call is idle
-  // one pool block: the addresses, then bucket b's table [nseg][k + 1 + b]
-  size_t words = host.size(), rows_at[CEC_FLAG_MULTI_MAX] = {};
-  for (int b = 1; b <= widest; ++b) {
-    rows_at[b - 1] = words;
-    words += nseg * (size_t)(k + 1 + b);
-  }
-  const size_t bytes = words * sizeof(uint64_t);
-  void* d = nullptr;
-  int rc = c->pool.alloc(bytes, &d);
-  if (rc) return rc;
-  // the segments' chunks: written and read on `st` only, so a large block is stream-ordered
-  const size_t chunk_words = widest < 1 ? 0 : cec::fs_chunk_words((uint32_t)k, (uint32_t)widest);
-  Scratch progs;
-  if (chunk_words) rc = scratch_alloc(c, nseg * chunk_words * sizeof(uint32_t), st, &progs);
-  hipError_t e = hipSuccess;
-  if (!rc) {
-    e = hipMemcpyAsync(d, host.data(), host.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
-                       c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess)
-      rc = set_err(CEC_EHIP, std::string("table upload: ") + hipGetErrorString(e));
-  }
-  if (rc) {
-    c->pool.retire(d, bytes);
-    scratch_release(c, progs, st);
-    return rc;
-  }
-  uint64_t* dw = static_cast<uint64_t*>(d);
   cec::FlagPlanMulti fp{};
-  fp.segs = dw;
   fp.flags = d_flags;
   fp.status = d_status;
-  for (int b = 1; b <= widest; ++b) fp.rows[b - 1] = dw + rows_at[b - 1];
-  fp.chunks = static_cast<uint32_t*>(progs.p);
-  fp.chunk_words = (uint32_t)chunk_words;
   fp.nseg = (uint32_t)nseg;
   fp.n = n;
   fp.k = k;
   fp.max_bad = max_bad;
-  cec::launch_flag_plan_multi(fp, st);
-  rc = check_launch();
-  for (int b = 1; b <= widest && !rc; ++b) {
-    cec::launch_ptrs_rt_flag(cec::rt_takes_rtb(c->opts, b, k), fp.rows[b - 1], fp.nseg,
-                             (uint32_t)(k + 1 + b), b, shard_len, vec_ok, st);
-    rc = check_launch();
-  }
-  const int mrc = c->pool.mark(st);  // the tables and the chunks stay until these complete
-  c->pool.retire(d, bytes);
-  scratch_release(c, progs, st);
-  return rc ? rc : mrc;
+  return run_flag_plan(c, host, 0, false, std::min({max_bad, c->m, most - k}), fp, shard_len,
+                       (bits & 15) == 0, st, [&](const cec::FlagPlanMulti& p, uint64_t*) {
+                         cec::launch_flag_plan_multi(p, st);
+                         return check_launch();
+                       });
 }
 
 int cec_repair_flagged_multi_ptrs(cec_codec* c, uint8_t* const* shards, const uint8_t* d_flags,
@@ -2138,9 +2163,8 @@ int cec_read_status(int k, int m, const uint8_t* held, const uint8_t* flags, con
 // cec_read_flagged_ptrs: cec_repair_flagged_multi_ptrs aimed at a destination. The host uploads
 // the shard addresses and the destinations and nothing else; the planner (kernels.h ReadPlan)
 // applies the rule, writes the copy rows of every segment and, for a rebuilt one, its program
-// chunk and its product row; the gated copy and one product launch per bucket follow it on `st`.
-// RS(2,1) takes k_ptr21's closed forms and needs no chunk. Nothing here waits for `st` or copies
-// from the device, and the decode cache is not touched.
+// chunk and its product row; the gated copy and one product launch per bucket follow it on `st`
+// (run_flag_plan). RS(2,1) takes k_ptr21's closed forms and needs no chunk.
 static int read_flagged_impl(cec_codec* c, const uint8_t* const* shards, const uint8_t* d_flags,
                              uint8_t* const* dst, size_t nseg, size_t shard_len, int max_bad,
                              uint8_t* d_status, hipStream_t st) {
@@ -2175,80 +2199,26 @@ static int read_flagged_impl(cec_codec* c, const uint8_t* const* shards, const u
     most = std::max(most, want);
   }
   const bool vec_ok = (bits & 15) == 0;
-  // a segment rebuilds its missing wanted data shards: at most max_bad, m (k good ones remain) and
-  // what it wants. < 1: nothing is wanted anywhere, every row of the call is idle
-  const int widest = std::min({max_bad, c->m, most});
-  // one pool block: the upload, the copy rows [nseg][k][2], then the product rows: RS(2,1)
-  // [nseg][4], else bucket b's table [nseg][k + 1 + b]
-  const size_t copy_at = host.size();
-  size_t words = copy_at + nseg * (size_t)k * cec::kRpCopyWords;
-  size_t rows_at[CEC_FLAG_MULTI_MAX] = {};
-  if (ct21) {
-    rows_at[0] = words;
-    words += nseg * cec::kRp21RowWords;
-  } else {
-    for (int b = 1; b <= widest; ++b) {
-      rows_at[b - 1] = words;
-      words += nseg * (size_t)cec::rp_row_words((uint32_t)k, (uint32_t)b);
-    }
-  }
-  const size_t bytes = words * sizeof(uint64_t);
-  void* d = nullptr;
-  int rc = c->pool.alloc(bytes, &d);
-  if (rc) return rc;
-  // the segments' chunks: written and read on `st` only, so a large block is stream-ordered
-  const size_t chunk_words =
-      ct21 || widest < 1 ? 0 : cec::fs_chunk_words((uint32_t)k, (uint32_t)widest);
-  Scratch progs;
-  if (chunk_words) rc = scratch_alloc(c, nseg * chunk_words * sizeof(uint32_t), st, &progs);
-  hipError_t e = hipSuccess;
-  if (!rc) {
-    e = hipMemcpyAsync(d, host.data(), host.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
-                       c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess)
-      rc = set_err(CEC_EHIP, std::string("table upload: ") + hipGetErrorString(e));
-  }
-  if (rc) {
-    c->pool.retire(d, bytes);
-    scratch_release(c, progs, st);
-    return rc;
-  }
-  uint64_t* dw = static_cast<uint64_t*>(d);
   cec::ReadPlan rp{};
-  rp.segs = dw;
-  rp.dst = dw + dst_at;
   rp.flags = d_flags;
   rp.status = d_status;
-  rp.copy = dw + copy_at;
-  if (ct21) rp.rows[0] = dw + rows_at[0];
-  else
-    for (int b = 1; b <= widest; ++b) rp.rows[b - 1] = dw + rows_at[b - 1];
-  rp.chunks = static_cast<uint32_t*>(progs.p);
-  rp.chunk_words = (uint32_t)chunk_words;
   rp.nseg = (uint32_t)nseg;
   rp.n = n;
   rp.k = k;
   rp.max_bad = max_bad;
-  cec::launch_read_plan(rp, ct21, st);
-  rc = check_launch();
-  if (!rc) {
-    cec::launch_read_copy(rp.copy, (uint64_t)nseg * k, shard_len, vec_ok, st);
-    rc = check_launch();
-  }
-  if (!rc && ct21) {
-    cec::launch_ptrs_rs21(cec::PtrSink::store, rp.rows[0], rp.nseg, shard_len, vec_ok, nullptr, st);
-    rc = check_launch();
-  }
-  for (int b = 1; !ct21 && b <= widest && !rc; ++b) {
-    cec::launch_ptrs_rt_flag(cec::rt_takes_rtb(c->opts, b, k), rp.rows[b - 1], rp.nseg,
-                             cec::rp_row_words((uint32_t)k, (uint32_t)b), b, shard_len, vec_ok, st);
-    rc = check_launch();
-  }
-  const int mrc = c->pool.mark(st);  // the tables and the chunks stay until these complete
-  c->pool.retire(d, bytes);
-  scratch_release(c, progs, st);
-  return rc ? rc : mrc;
+  // a segment rebuilds its missing wanted data shards: at most max_bad, m (k good ones remain) and
+  // what it wants. < 1: nothing is wanted anywhere, every row of the call is idle. The copy rows
+  // [nseg][k][2] lie between the upload and the product rows
+  return run_flag_plan(c, host, nseg * (size_t)k * cec::kRpCopyWords, ct21,
+                       std::min({max_bad, c->m, most}), rp, shard_len, vec_ok, st,
+                       [&](cec::ReadPlan& p, uint64_t* copy_rows) {
+                         p.dst = p.segs + dst_at;
+                         p.copy = copy_rows;
+                         cec::launch_read_plan(p, ct21, st);
+                         if (int rc = check_launch()) return rc;
+                         cec::launch_read_copy(p.copy, (uint64_t)nseg * k, shard_len, vec_ok, st);
+                         return check_launch();
+                       });
 }
 
 int cec_read_flagged_ptrs(cec_codec* c, const uint8_t* const* shards, const uint8_t* d_flags,

@@ -187,51 +187,41 @@ void launch_flag_plan(const FlagPlan& p, bool rs21, hipStream_t st);
 void launch_ptrs_rt_flag(bool bitplane, const uint64_t* tab, uint32_t nrows, uint32_t rs, int nob,
                          uint64_t len, bool vec_ok, hipStream_t st);
 
-// Several bad shards per segment (cec_repair_flagged_multi_ptrs): the planner also solves the
-// decode rows, per segment, from the flags (flag_solve.h: the Lagrange form, no inversion), so the
-// host prepares no program. The rule is cec_flag_status_multi's: up to max_bad (<= kFlagMultiMax)
-// bad shards and >= k good ones: rebuilt, all of them, from the first k good shards in index order.
+// Several bad shards per segment (cec_repair_flagged_multi_ptrs), and a degraded read decided on
+// the GPU (cec_read_flagged_ptrs): the planner also solves the decode rows, per segment, from the
+// flags (flag_solve.h: the Lagrange form, no inversion), so the host prepares no program. Both are
+// one wave program under a rule (flag_solve.h FsRepair, read_plan.h RpRead) and take one plan.
+// The repair's rule is cec_flag_status_multi's: up to max_bad (<= kFlagMultiMax) bad shards and
+// >= k good ones: rebuilt, all of them, where they lie, from the first k good shards in index
+// order. The read's is cec_read_status's, with the missing wanted data shards (wanted and not
+// held, or held with flag 0) in the place of the bad ones: they are rebuilt at the caller's
+// destinations and the good wanted ones copied there; nothing at `segs` is ever an output.
 struct FlagPlanMulti {
   const uint64_t* segs;   // [nseg][n]: a segment's n shard addresses (0: not held)
   const uint8_t* flags;   // [nseg][n], any alignment; bytes of shards not held are not read
   uint8_t* status;        // [nseg]: kFlag* per segment
   uint64_t* rows[4];      // rows[b - 1]: the table of bucket b, [nseg][k + 1 + b] words; null: no
-                          // segment of the call can have b bad shards rebuilt, no table
-  uint32_t* chunks;       // [nseg][chunk_words]: segment s's program chunk (flag_solve.h)
+                          // segment of the call can have b shards rebuilt, no table. A read of
+                          // RS(2,1): rows[0] is [nseg][4], k_ptr21's rows
+  uint32_t* chunks;       // [nseg][chunk_words]: segment s's program chunk (flag_solve.h; unused
+                          // for RS(2,1))
   uint32_t chunk_words;   // fs_chunk_words(k, the widest bucket with a table)
   uint32_t nseg;
   int n, k, max_bad;
-};
-// One wave per segment. A segment rebuilt with e bad shards gets the row {its chunk, the addresses
-// of its first k good shards, of its e bad ones} in bucket e's table and its chunk written (header
-// {k, e, e, 0}, hb, masks); in every other table its row is idle: word 0 zero, the rest unwritten.
-// Row s and chunk s are segment s's: no atomics, no compaction, the tables of two runs are equal.
-void launch_flag_plan_multi(const FlagPlanMulti& p, hipStream_t st);
-
-// A degraded read decided on the GPU (cec_read_flagged_ptrs, read_plan.h): the wanted data shards
-// of a segment arrive at the caller's destinations, the good ones copied, the missing ones
-// (wanted and not held, or held with flag 0) rebuilt from the first k good shards. The rule is
-// cec_read_status's: nothing missing: clean; fewer than k good: lost; up to max_bad missing:
-// rebuilt; else many. Nothing at `segs` is ever an output.
-struct ReadPlan {
-  const uint64_t* segs;   // [nseg][n]: a segment's n shard addresses (0: not held)
+  // a read only, null for a repair
   const uint64_t* dst;    // [nseg][k]: where data shard j is wanted (0: not wanted)
-  const uint8_t* flags;   // [nseg][n], any alignment; bytes of shards not held are not read
-  uint8_t* status;        // [nseg]: kFlag* per segment
   uint64_t* copy;         // [nseg][k][2]: {src, dst} of every good wanted data shard of a clean or
                           // rebuilt segment, {0, 0} elsewhere
-  uint64_t* rows[4];      // any code: rows[b - 1] is the table of bucket b, [nseg][k + 1 + b]
-                          // words (null: no table); RS(2,1): rows[0] is [nseg][4], k_ptr21's rows
-  uint32_t* chunks;       // [nseg][chunk_words]: segment s's program chunk (unused for RS(2,1))
-  uint32_t chunk_words;   // fs_chunk_words(k, the widest bucket with a table)
-  uint32_t nseg;
-  int n, k, max_bad;
 };
+using ReadPlan = FlagPlanMulti;
+// One wave per segment. A segment rebuilt with e shards gets the row {its chunk, the addresses of
+// its first k good shards, of its e outputs} in bucket e's table and its chunk written (header
+// {k, e, e, 0}, hb, masks); in every other table its row is idle: word 0 zero, and for a repair
+// the rest unwritten, for a read zero in every word. Row s and chunk s are segment s's, written
+// with plain stores: no atomics, no compaction, the tables of two runs are equal.
+void launch_flag_plan_multi(const FlagPlanMulti& p, hipStream_t st);
 // rs21: one lane per segment, rows {input 0, input 1, destination, case 0 / 1} or the idle {0, 0,
-// 0, 3}. Otherwise one wave per segment: a segment rebuilt with e missing shards gets {its chunk,
-// its first k good shards, the e destinations} in bucket e's table and its chunk written; its row
-// in every other table, and every row of a segment that is not rebuilt, is zero in every word.
-// Rows are written whole with plain stores, row s is segment s's: the tables of two runs are equal.
+// 0, 3}. Otherwise the wave program above under the read's rule, which also writes the copy rows.
 void launch_read_plan(const ReadPlan& p, bool rs21, hipStream_t st);
 // The gated copy: `nrows` rows {src, dst}; a workgroup row whose src word is zero leaves after one
 // scalar load, every other streams `len` bytes from src to dst (16-byte columns with a byte tail,

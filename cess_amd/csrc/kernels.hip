@@ -1999,18 +1999,22 @@ __global__ __launch_bounds__(256) void k_flag_plan(FlagPlan p) {
   }
 }
 
-// Several bad shards per segment (kernels.h FlagPlanMulti): the wave of a segment also solves its
-// decode rows (flag_solve.h) and writes its program chunk. The lanes stride over the n flags; the
-// ballots give the counts, the first k good indices (in LDS, 256 bytes per wave, written and read
-// by this wave only) and the first four bad ones (wave-uniform, a byte each of one word). Then the
-// lanes stride over the k survivors: lane t writes survivor t's address into the row and input
-// column t into the chunk. N_j is computed by every lane for itself.
+// Several bad shards per segment, and a degraded read (kernels.h FlagPlanMulti): the wave of a
+// segment also solves its decode rows (flag_solve.h) and writes its program chunk. One body under
+// a rule, FsRepair (flag_solve.h) or RpRead (read_plan.h), which says which shards are lost, where
+// an output goes, what an idle row gets and whether there are copy rows. The lanes stride over the
+// n flags; the ballots give the counts, the first k good indices (in LDS, 256 bytes per wave,
+// written and read by this wave only) and the first four lost ones (wave-uniform, a byte each of
+// one word). Then the lanes stride over k for the copy rows, and for a rebuilt segment over the k
+// survivors: lane t writes survivor t's address into the row and input column t into the chunk.
+// N_j is computed by every lane for itself.
 static_assert(kFsHeaderWords == kRtHeaderWords, "flag_solve.h writes the chunk layout of kernels.h");
 static_assert(kFlagMultiMax == 4, "one table per bucket of the bit-plane product");
 static_assert(kFsClean == kFlagClean && kFsRebuilt == kFlagRebuilt && kFsMany == kFlagMany &&
                   kFsLost == kFlagLost,
               "one set of status codes");
-__global__ __launch_bounds__(256) void k_flag_plan_multi(FlagPlanMulti p) {
+template <class Rule>
+__device__ __forceinline__ void plan_wave(const FlagPlanMulti& p) {
   __shared__ uint8_t surv_all[4][256];
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t s = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -2018,31 +2022,39 @@ __global__ __launch_bounds__(256) void k_flag_plan_multi(FlagPlanMulti p) {
   uint8_t* surv = surv_all[threadIdx.x >> 6];
   const uint32_t n = (uint32_t)p.n, k = (uint32_t)p.k;
   const uint64_t* __restrict__ seg = p.segs + s * n;
+  const uint64_t* __restrict__ dp = Rule::kCopies ? p.dst + s * k : nullptr;
   const uint8_t* __restrict__ fl = p.flags + s * n;
-  uint32_t nbad = 0, ngood = 0, lost = 0;
+  uint32_t nlost = 0, ngood = 0, lost = 0;
   for (uint32_t base = 0; base < n; base += 64) {
     const uint32_t i = base + lane;
     const bool held = i < n && seg[i] != 0;
     const bool good = held && fl[i] != 0;
-    unsigned long long bad = __ballot(held && !good);
+    unsigned long long lm = __ballot(Rule::lost(held, good, i, k, dp));
     const unsigned long long gm = __ballot(good);
     const uint32_t pos = ngood + (uint32_t)__popcll(gm & ((1ull << lane) - 1));
     if (good && pos < k) surv[pos] = (uint8_t)i;
     ngood += (uint32_t)__popcll(gm);
-    for (; bad; bad &= bad - 1) {
-      if (nbad < 4) lost |= (base + (uint32_t)__ffsll(bad) - 1) << (8 * nbad);
-      ++nbad;
+    for (; lm; lm &= lm - 1) {
+      if (nlost < 4) lost |= (base + (uint32_t)__ffsll(lm) - 1) << (8 * nlost);
+      ++nlost;
     }
   }
-  const uint32_t st = fs_status(nbad, ngood, k, (uint32_t)p.max_bad);
-  const uint32_t e = st == kFlagRebuilt ? nbad : 0;
-  uint64_t* row = nullptr;  // the segment's row in bucket e's table
+  const uint32_t st = fs_status(nlost, ngood, k, (uint32_t)p.max_bad);
+  const uint32_t e = st == kFlagRebuilt ? nlost : 0;
   if (lane == 0) p.status[s] = (uint8_t)st;
+  if constexpr (Rule::kCopies) {  // data shard j, wanted and good, of a segment that is read
+    uint64_t* __restrict__ cp = p.copy + s * k * kRpCopyWords;
+    for (uint32_t j = lane; j < k; j += 64) {
+      const uint64_t a = seg[j], d = dp[j];
+      Rule::put_copy(cp, j, Rule::copied(st, d != 0, a != 0 && fl[j] != 0), a, d);
+    }
+  }
+  uint64_t* row = nullptr;  // the segment's row in bucket e's table
 #pragma unroll
   for (uint32_t b = 1; b <= 4; ++b) {
-    uint64_t* const rb = p.rows[b - 1] ? p.rows[b - 1] + s * (k + 1 + b) : nullptr;
+    uint64_t* const rb = p.rows[b - 1] ? p.rows[b - 1] + s * fs_row_words(k, b) : nullptr;
     if (b == e) row = rb;
-    else if (rb && lane == 0) rb[0] = 0;
+    else if (rb) Rule::put_idle(rb, fs_row_words(k, b), lane, 64);
   }
   if (!row) return;  // no rebuild (a rebuilt segment's bucket always has a table)
   // the survivor list is complete: LDS accesses of one wave complete in order
@@ -2050,31 +2062,24 @@ __global__ __launch_bounds__(256) void k_flag_plan_multi(FlagPlanMulti p) {
   __builtin_amdgcn_wave_barrier();
   uint32_t* __restrict__ chunk = p.chunks + s * p.chunk_words;
   uint32_t nj[4];
-#pragma unroll
-  for (uint32_t o = 0; o < 4; ++o) nj[o] = o < e ? fs_numer(surv, k, (lost >> (8 * o)) & 0xFFu) : 0;
+  fs_solve_begin(surv, k, e, lost, nj, lane == 0 ? chunk : nullptr);
   if (lane == 0) {
-    fs_put_header(chunk, k, e);
-    row[0] = (uint64_t)(uintptr_t)chunk;
+    fs_put_chunk(row, (uint64_t)(uintptr_t)chunk);
 #pragma unroll
     for (uint32_t o = 0; o < 4; ++o)
-      if (o < e) row[1 + k + o] = seg[(lost >> (8 * o)) & 0xFFu];
+      if (o < e) fs_put_out(row, k, o, Rule::out_addr(seg, dp, fs_lost(lost, o)));
   }
   for (uint32_t t = lane; t < k; t += 64) {
-    const uint32_t sv = surv[t];
-    row[1 + t] = seg[sv];
-    const uint32_t dt = fs_denom(surv, k, t);
-    uint32_t col = 0;
-#pragma unroll
-    for (uint32_t o = 0; o < 4; ++o)
-      if (o < e) col |= fs_coef(nj[o], (lost >> (8 * o)) & 0xFFu, sv, dt) << (8 * o);
-    fs_put_column(chunk, e, t, col);
+    fs_put_in(row, t, seg[surv[t]]);
+    fs_solve_column(surv, k, e, lost, nj, t, chunk);
   }
 }
+__global__ __launch_bounds__(256) void k_flag_plan_multi(FlagPlanMulti p) { plan_wave<FsRepair>(p); }
 
-// The planners of a degraded read (kernels.h ReadPlan, read_plan.h): the repair's planners with
-// "missing" counted over the wanted data shards, shards that are not held included, the output
-// addresses taken from the caller's destinations, and the copy rows of the good wanted data shards
-// written beside the product rows. Nothing of `segs` becomes an output.
+// The planners of a degraded read (read_plan.h): the repair's with "missing" counted over the
+// wanted data shards, shards that are not held included, the output addresses taken from the
+// caller's destinations, and the copy rows of the good wanted data shards written beside the
+// product rows. Nothing of `segs` becomes an output.
 
 // RS(2,1): one lane per segment (rp_plan21).
 __global__ __launch_bounds__(256) void k_read_plan21(ReadPlan p) {
@@ -2094,78 +2099,8 @@ __global__ __launch_bounds__(256) void k_read_plan21(ReadPlan p) {
   }
 }
 
-// Any code: k_flag_plan_multi's shape, one wave per segment, four per workgroup, the lanes
-// striding over n for the ballots (counts, the first k good indices in LDS, the first four missing
-// ones in a word), then over k for the copy rows, and for a rebuilt segment over the k survivors.
-__global__ __launch_bounds__(256) void k_read_plan(ReadPlan p) {
-  __shared__ uint8_t surv_all[4][256];
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t s = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (s >= p.nseg) return;  // the whole wave
-  uint8_t* surv = surv_all[threadIdx.x >> 6];
-  const uint32_t n = (uint32_t)p.n, k = (uint32_t)p.k;
-  const uint64_t* __restrict__ seg = p.segs + s * n;
-  const uint64_t* __restrict__ dp = p.dst + s * k;
-  const uint8_t* __restrict__ fl = p.flags + s * n;
-  uint32_t nmiss = 0, ngood = 0, lost = 0;
-  for (uint32_t base = 0; base < n; base += 64) {
-    const uint32_t i = base + lane;
-    const bool held = i < n && seg[i] != 0;
-    const bool good = rp_good(held, held ? fl[i] : 0);
-    const bool wanted = i < k && dp[i] != 0;
-    unsigned long long miss = __ballot(rp_missing(wanted, good));
-    const unsigned long long gm = __ballot(good);
-    const uint32_t pos = ngood + (uint32_t)__popcll(gm & ((1ull << lane) - 1));
-    if (good && pos < k) surv[pos] = (uint8_t)i;
-    ngood += (uint32_t)__popcll(gm);
-    for (; miss; miss &= miss - 1) {
-      if (nmiss < 4) lost |= (base + (uint32_t)__ffsll(miss) - 1) << (8 * nmiss);
-      ++nmiss;
-    }
-  }
-  const uint32_t st = rp_status(nmiss, ngood, k, (uint32_t)p.max_bad);
-  const uint32_t e = st == kFlagRebuilt ? nmiss : 0;
-  if (lane == 0) p.status[s] = (uint8_t)st;
-  // the copy rows: data shard j, wanted and good, of a segment that is read
-  uint64_t* __restrict__ cp = p.copy + s * k * kRpCopyWords;
-  const bool copies = rp_copies(st);
-  for (uint32_t j = lane; j < k; j += 64) {
-    const uint64_t a = seg[j], d = dp[j];
-    rp_put_copy(cp, j, copies && d != 0 && rp_good(a != 0, a ? fl[j] : 0), a, d);
-  }
-  uint64_t* row = nullptr;  // the segment's row in bucket e's table
-#pragma unroll
-  for (uint32_t b = 1; b <= 4; ++b) {
-    uint64_t* const rb = p.rows[b - 1] ? p.rows[b - 1] + s * rp_row_words(k, b) : nullptr;
-    if (b == e) row = rb;
-    else if (rb) rp_put_idle(rb, rp_row_words(k, b), lane, 64);
-  }
-  if (!row) return;  // no rebuild (a rebuilt segment's bucket always has a table)
-  // the survivor list is complete: LDS accesses of one wave complete in order
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  uint32_t* __restrict__ chunk = p.chunks + s * p.chunk_words;
-  uint32_t nj[4];
-#pragma unroll
-  for (uint32_t o = 0; o < 4; ++o) nj[o] = o < e ? fs_numer(surv, k, (lost >> (8 * o)) & 0xFFu) : 0;
-  if (lane == 0) {
-    fs_put_header(chunk, k, e);
-    rp_put_chunk(row, (uint64_t)(uintptr_t)chunk);
-#pragma unroll
-    for (uint32_t o = 0; o < 4; ++o)
-      if (o < e) rp_put_out(row, k, o, dp[(lost >> (8 * o)) & 0xFFu]);
-  }
-  for (uint32_t t = lane; t < k; t += 64) {
-    const uint32_t sv = surv[t];
-    rp_put_in(row, t, seg[sv]);
-    const uint32_t dt = fs_denom(surv, k, t);
-    uint32_t col = 0;
-#pragma unroll
-    for (uint32_t o = 0; o < 4; ++o)
-      if (o < e) col |= fs_coef(nj[o], (lost >> (8 * o)) & 0xFFu, sv, dt) << (8 * o);
-    fs_put_column(chunk, e, t, col);
-  }
-}
+// Any code: the wave program under the read's rule.
+__global__ __launch_bounds__(256) void k_read_plan(ReadPlan p) { plan_wave<RpRead>(p); }
 
 // The gated copy of a read: row = {src, dst} in one scalar load, a zero src ends the workgroup
 // there. U 16-byte columns per lane, all loads issued before the first store, with the streamed
