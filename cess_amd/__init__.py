@@ -15,6 +15,11 @@ from ._lib import (
     CEC_FLAG_MULTI_MAX,
     CEC_FLAG_REBUILT,
     CEC_HASHQ_SKIPPED,
+    CEC_LOCATE_AMBIGUOUS,
+    CEC_LOCATE_CLEAN,
+    CEC_LOCATE_FOUND,
+    CEC_LOCATE_SYN_MAX,
+    CEC_LOCATE_UNCHECKED,
 )
 from .hashq import HashQueue, sha256_blocks
 from .records import ErrTooManySegments
@@ -37,6 +42,8 @@ from .reedsolomon import (
     fill_synthetic,
     flag_status,
     flag_status_multi,
+    locate_host,
+    locate_rows,
     read_status,
     sha256_hex_device,
     sha256_hex_host,
@@ -52,4 +59,6 @@ __all__ = [
     "CEC_FLAG_MANY", "CEC_FLAG_LOST", "CEC_FLAG_MULTI_MAX", "flag_status_multi",
     "confirm_flagged", "confirm_rule", "CEC_CONFIRM_NONE", "CEC_CONFIRM_PROVEN",
     "CEC_CONFIRM_REFUTED", "CEC_HASHQ_SKIPPED", "read_status",
+    "locate_rows", "locate_host", "CEC_LOCATE_SYN_MAX", "CEC_LOCATE_CLEAN", "CEC_LOCATE_FOUND",
+    "CEC_LOCATE_AMBIGUOUS", "CEC_LOCATE_UNCHECKED",
 ]

@@ -104,6 +104,12 @@ SIGNATURES = {
                                POINTER(c_int)]),
     "cec_read_flagged_ptrs": (c_int, [c_void_p, POINTER(c_void_p), c_void_p, POINTER(c_void_p),
                                       c_size_t, c_size_t, c_int, c_void_p, c_void_p]),
+    "cec_locate_rows": (c_int, [c_int, c_int, POINTER(c_uint8), c_int, POINTER(c_int),
+                                POINTER(c_uint8)]),
+    "cec_locate_host": (c_int, [c_int, c_int, POINTER(c_void_p), c_size_t, c_int, POINTER(c_int),
+                                POINTER(c_int)]),
+    "cec_locate_ptrs": (c_int, [c_void_p, POINTER(c_void_p), c_size_t, c_size_t, c_int, c_void_p,
+                                c_void_p, c_void_p]),
     "cec_encode_idx_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_size_t,
                                      c_size_t, c_int, c_void_p]),
     "cec_update_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,
@@ -256,6 +262,11 @@ CEC_FLAG_REBUILT = 1
 CEC_FLAG_MANY = 2
 CEC_FLAG_LOST = 3
 CEC_FLAG_MULTI_MAX = 4
+CEC_LOCATE_SYN_MAX = 4
+CEC_LOCATE_CLEAN = 0
+CEC_LOCATE_FOUND = 1
+CEC_LOCATE_AMBIGUOUS = 2
+CEC_LOCATE_UNCHECKED = 3
 CEC_CONFIRM_NONE = 0
 CEC_CONFIRM_PROVEN = 1
 CEC_CONFIRM_REFUTED = 2

@@ -275,3 +275,106 @@ def scrub_repair_confirm_device(enc: Encoder, segments: Sequence, recorded, max_
     cap = 1 << max(0, nseg * n - 1).bit_length()
     with HashQueue(capacity=cap, device=enc.device, stream=torch.cuda.current_stream(dev)) as q:
         return go(q)
+
+
+def _queue_stream(q):
+    """(the stream handle the C calls take, torch's view of the same stream) of a HashQueue."""
+    import torch
+    if q.stream is None:  # a queue without one: the null stream
+        return 0, torch.cuda.default_stream(q.device)
+    if isinstance(q.stream, int):
+        return q.stream, torch.cuda.ExternalStream(q.stream, device=q.device)
+    return q.stream, q.stream
+
+
+def locate_repair_device(enc: Encoder, segments: Sequence, nsyn: int = _lib.CEC_LOCATE_SYN_MAX,
+                         recorded=None, queue=None):
+    """A scrub at the parity rate that heals what it finds: Encoder.LocateDevice names the one
+    fragment of a segment that disagrees with the others, from parity alone, and
+    Encoder.RepairFlaggedDevice reads those flags on the same stream and rebuilds it in place.
+    `segments` as in scrub_repair_device. Without `recorded` nothing is hashed and the stream is
+    torch's current one, or `queue`'s: returns (d_flags [nseg][k + m], d_locate [nseg] of
+    CEC_LOCATE_* codes, d_status [nseg] of CEC_FLAG_* codes). With `recorded` (per segment k + m
+    64-byte hashes, or one tensor [nseg][k + m][64]) the proof of scrub_repair_confirm_device
+    follows: exactly the rebuilt fragments are hashed (HashQueue.add_check_where_ptrs gated on
+    CEC_FLAG_REBUILT) and confirm_flagged folds the result: returns (d_flags, d_locate, d_status,
+    d_ok [nseg][k + m], d_confirm [nseg]). A FOUND segment is REBUILT; an AMBIGUOUS one has every
+    held flag 0, so the repair reports LOST and writes nothing. Nothing is waited for. queue None
+    with `recorded`: a queue of the table's size on torch's current stream, owned and closed by
+    the call."""
+    import torch
+    from .hashq import HashQueue
+    segments = [list(seg) for seg in segments]
+    nseg, n = len(segments), enc.Shards
+    if any(len(seg) != n for seg in segments):
+        raise ErrInvalidInput(ErrInvalidInput.__doc__)
+    dev = torch.device("cuda", enc.device)
+
+    def heal(stream):
+        d_flags, d_locate = enc.LocateDevice(segments, nsyn=nsyn, stream=stream)
+        return d_flags, d_locate, enc.RepairFlaggedDevice(segments, d_flags, stream=stream)
+
+    if recorded is None:
+        return heal(torch.cuda.current_stream(dev) if queue is None else _queue_stream(queue)[0])
+    _, slots, rec, _, _ = _scrub_table(enc, segments, recorded)
+
+    def go(q):
+        stream = _queue_stream(q)[0]
+        d_flags, d_locate, d_status = heal(stream)
+        d_ok = torch.empty((nseg, n), dtype=torch.uint8, device=dev)
+        flat, ok = d_flags.view(-1), d_ok.view(-1)
+        step = max(1, q.capacity // n)  # whole segments per slice
+        for s0 in range(0, nseg, step):
+            s1 = min(nseg, s0 + step)
+            a, b = s0 * n, s1 * n
+            q.add_check_where_ptrs(slots[a:b], rec[a:b], flat[a:b], per=n, d_gate=d_status[s0:s1],
+                                   gate=_lib.CEC_FLAG_REBUILT, d_ok=ok[a:b])
+            q.finish()
+        return d_flags, d_locate, d_status, d_ok, confirm_flagged(d_status, d_ok, n, stream=stream)
+
+    if queue is not None:
+        return go(queue)
+    cap = 1 << max(0, nseg * n - 1).bit_length()
+    with HashQueue(capacity=cap, device=enc.device, stream=torch.cuda.current_stream(dev)) as q:
+        return go(q)
+
+
+def scrub_located_device(enc: Encoder, segments: Sequence, recorded,
+                         nsyn: int = _lib.CEC_LOCATE_SYN_MAX, queue=None):
+    """A scrub that hashes only what parity cannot settle, RS(2,1) included: Encoder.LocateDevice
+    over the table, then HashQueue.add_check_where_ptrs over all of it with per = k + m, d_gate =
+    the locate codes and gate = CEC_LOCATE_AMBIGUOUS, so exactly the held fragments of the
+    inconsistent segments no single shard explains (with one parity shard: of every inconsistent
+    segment) get a checked chain, ticked to completion; every other fragment is CEC_HASHQ_SKIPPED
+    and no byte of it is hashed. The two are merged on the device: flags = where(d_ok == SKIPPED,
+    located flags, d_ok). Arguments as in scrub_repair_device. Returns (d_flags [nseg][k + m],
+    d_locate [nseg]): flags ready for the flagged repairs and the flagged read. Nothing is waited
+    for. A caller's queue has to be idle and hold at least k + m chains."""
+    import torch
+    from .hashq import HashQueue
+    segments, slots, rec, _, _ = _scrub_table(enc, segments, recorded)
+    nseg, n = len(segments), enc.Shards
+    dev = torch.device("cuda", enc.device)
+
+    def go(q):
+        stream, tstream = _queue_stream(q)
+        d_flags, d_locate = enc.LocateDevice(segments, nsyn=nsyn, stream=stream)
+        d_ok = torch.empty((nseg, n), dtype=torch.uint8, device=dev)
+        flat, ok = d_flags.view(-1), d_ok.view(-1)
+        step = max(1, q.capacity // n)  # whole segments per slice
+        for s0 in range(0, nseg, step):
+            s1 = min(nseg, s0 + step)
+            a, b = s0 * n, s1 * n
+            q.add_check_where_ptrs(slots[a:b], rec[a:b], flat[a:b], per=n,
+                                   d_gate=d_locate[s0:s1], gate=_lib.CEC_LOCATE_AMBIGUOUS,
+                                   d_ok=ok[a:b])
+            q.finish()
+        with torch.cuda.stream(tstream):
+            merged = torch.where(d_ok == _lib.CEC_HASHQ_SKIPPED, d_flags, d_ok)
+        return merged, d_locate
+
+    if queue is not None:
+        return go(queue)
+    cap = 1 << max(0, nseg * n - 1).bit_length()
+    with HashQueue(capacity=cap, device=enc.device, stream=torch.cuda.current_stream(dev)) as q:
+        return go(q)

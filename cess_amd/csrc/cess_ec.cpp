@@ -33,6 +33,7 @@
 #include "fftdec_plan.h"
 #include "flag_solve.h"
 #include "read_plan.h"
+#include "locate_rule.h"
 #include "gf256.h"
 #include "hashq_where.h"
 #include "host_util.h"
@@ -2232,6 +2233,180 @@ int cec_read_flagged_ptrs(cec_codec* c, const uint8_t* const* shards, const uint
   CEC_HIP_TRY(hipSetDevice(c->device));
   return read_flagged_impl(c, shards, d_flags, dst, nseg, shard_len, max_bad, d_status,
                            pick_stream(c, hip_stream));
+}
+
+// ---- the corrupt shard from parity alone (locate_rule.h) ---------------------------------------
+
+static_assert(CEC_LOCATE_SYN_MAX == cec::kLocateSynMax, "one syndrome product per bucket");
+static_assert(CEC_LOCATE_CLEAN == cec::kLocClean && CEC_LOCATE_FOUND == cec::kLocFound &&
+                  CEC_LOCATE_AMBIGUOUS == cec::kLocAmbiguous &&
+                  CEC_LOCATE_UNCHECKED == cec::kLocUnchecked,
+              "locate_rule.h states the rule in the header's codes");
+
+static int check_locate(int k, int m, int nsyn) {
+  if (k < 1 || m < 1 || k + m > cec::kMaxShards)
+    return set_err(CEC_EINVAL, "need k >= 1, m >= 1, k + m <= 256");
+  if (nsyn < 1 || nsyn > CEC_LOCATE_SYN_MAX)
+    return set_err(CEC_EINVAL, "nsyn must be 1..CEC_LOCATE_SYN_MAX");
+  return CEC_OK;
+}
+
+int cec_locate_rows(int k, int m, const uint8_t* held, int nsyn, int* r, uint8_t* rows) {
+  if (!held || !r || !rows) return set_err(CEC_EINVAL, "null");
+  if (int rc = check_locate(k, m, nsyn)) return rc;
+  const uint32_t n = (uint32_t)(k + m);
+  uint8_t H[cec::kMaxShards];
+  uint32_t h = 0;
+  for (uint32_t i = 0; i < n; ++i)
+    if (held[i]) H[h++] = (uint8_t)i;
+  const uint32_t rr = cec::loc_r(h, (uint32_t)k, (uint32_t)nsyn);
+  std::memset(rows, 0, (size_t)CEC_LOCATE_SYN_MAX * n);
+  for (uint32_t t = 0; t < h && rr; ++t) {
+    const uint32_t col = cec::loc_column(H, h, t);
+    for (uint32_t a = 0; a < rr; ++a) rows[(size_t)a * n + H[t]] = (uint8_t)(col >> (8 * a));
+  }
+  *r = (int)rr;
+  return CEC_OK;
+}
+
+int cec_locate_host(int k, int m, const uint8_t* const* shards, size_t shard_len, int nsyn,
+                    int* status, int* found) {
+  if (!shards || !status || !found) return set_err(CEC_EINVAL, "null");
+  if (int rc = check_locate(k, m, nsyn)) return rc;
+  uint32_t st = 0;
+  cec::loc_segment_host((uint32_t)k, (uint32_t)(k + m), shards, shard_len, (uint32_t)nsyn, &st,
+                        found);
+  *status = (int)st;
+  return CEC_OK;
+}
+
+// cec_locate_ptrs: the held sets are the NULL pattern, so the host knows them all. One pool block:
+// the upload ([nseg][most + 2] rows {chunk, held addresses in index order, ..., set}, the sets'
+// planner tables, the sets' program chunks), then what the kernels keep between them (witness,
+// candidate, dirty, dirty2 per segment), preset on `st`. One grid of the syndrome product per
+// value of r in the call, the planner, the confirm grids, the finish. Nothing here waits for `st`
+// or copies from the device, and the decode cache is not touched.
+static int locate_impl(cec_codec* c, const uint8_t* const* shards, size_t nseg, size_t shard_len,
+                       int nsyn, uint8_t* d_flags, uint8_t* d_status, hipStream_t st) {
+  const uint32_t n = (uint32_t)(c->k + c->m), k = (uint32_t)c->k;
+  struct Set {
+    std::string key;
+    uint32_t h, r;
+    size_t chunk_at;  // word offset of its chunk in the block (r >= 1)
+  };
+  std::unordered_map<std::string, size_t> gidx;
+  std::vector<Set> sets;
+  std::vector<uint32_t> set_of(nseg);
+  std::string key((size_t)n, '\0');
+  uintptr_t bits = 0;  // OR of every held address: the alignment of the call
+  uint32_t most = 0;
+  bool has_r[CEC_LOCATE_SYN_MAX + 1] = {};
+  for (size_t s = 0; s < nseg; ++s) {
+    uint32_t h = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint8_t* const a = shards[s * n + i];
+      key[i] = a ? 1 : 0;
+      h += a ? 1 : 0;
+      bits |= (uintptr_t)a;
+    }
+    const size_t gi = group_of(gidx, key, sets.size());
+    set_of[s] = (uint32_t)gi;
+    if (gi < sets.size()) continue;
+    const uint32_t r = cec::loc_r(h, k, (uint32_t)nsyn);
+    sets.push_back({key, h, r, 0});
+    most = std::max(most, h);
+    has_r[r] = true;
+  }
+  const bool vec_ok = (bits & 15) == 0;
+  const uint32_t rs = most + 2, set_bytes = cec::loc_set_bytes(n);
+  const size_t sets_at = nseg * rs;
+  size_t in_words = sets_at + sets.size() * (set_bytes / 8);
+  for (Set& g : sets) {
+    if (!g.r) continue;
+    g.chunk_at = in_words;
+    in_words += (cec::fs_chunk_words(g.h, g.r) + 1) / 2;
+  }
+  const size_t wit_at = in_words, cand_at = wit_at + nseg, dirty_at = cand_at + (nseg + 1) / 2;
+  const size_t words = dirty_at + (2 * nseg + 7) / 8;
+  const size_t bytes = words * sizeof(uint64_t);
+  void* d = nullptr;
+  int rc = c->pool.alloc(bytes, &d);
+  if (rc) return rc;
+  uint64_t* dw = static_cast<uint64_t*>(d);
+  std::vector<uint64_t> host(in_words, 0);
+  for (size_t g = 0; g < sets.size(); ++g) {
+    const Set& set = sets[g];
+    cec::loc_put_set(reinterpret_cast<uint8_t*>(host.data() + sets_at) + g * set_bytes,
+                     reinterpret_cast<const uint8_t*>(set.key.data()), n, set.r);
+    if (!set.r) continue;
+    uint8_t H[cec::kMaxShards];
+    uint32_t h = 0;
+    for (uint32_t i = 0; i < n; ++i)
+      if (set.key[i]) H[h++] = (uint8_t)i;
+    cec::loc_put_chunk(reinterpret_cast<uint32_t*>(host.data() + set.chunk_at), H, h, set.r);
+  }
+  for (size_t s = 0; s < nseg; ++s) {
+    const Set& set = sets[set_of[s]];
+    uint64_t* row = host.data() + s * rs;
+    row[rs - 1] = set_of[s];
+    if (!set.r) continue;  // unchecked: no chunk and no address goes to the device
+    row[0] = (uint64_t)(uintptr_t)(dw + set.chunk_at);
+    uint32_t t = 0;
+    for (uint32_t i = 0; i < n; ++i)
+      if (shards[s * n + i]) row[1 + t++] = (uint64_t)(uintptr_t)shards[s * n + i];
+  }
+  rc = upload_table(c, d, host.data(), in_words);
+  if (rc) {
+    c->pool.retire(d, bytes);
+    return rc;
+  }
+  cec::LocatePlan lp{};
+  lp.rows = dw;
+  lp.sets = reinterpret_cast<const uint8_t*>(dw + sets_at);
+  lp.witness = dw + wit_at;
+  lp.cand = reinterpret_cast<uint32_t*>(dw + cand_at);
+  lp.dirty = reinterpret_cast<uint8_t*>(dw + dirty_at);
+  lp.dirty2 = lp.dirty + nseg;
+  lp.flags = d_flags;
+  lp.status = d_status;
+  lp.rs = rs;
+  lp.set_bytes = set_bytes;
+  lp.nseg = (uint32_t)nseg;
+  lp.n = (int)n;
+  lp.k = (int)k;
+  hipError_t e = hipMemsetAsync(lp.witness, 0xFF, nseg * sizeof(uint64_t), st);
+  if (e == hipSuccess) e = hipMemsetAsync(lp.dirty, 0, 2 * nseg, st);
+  if (e != hipSuccess) rc = set_err(CEC_EHIP, std::string("locate preset: ") + hipGetErrorString(e));
+  for (int r = 1; r <= CEC_LOCATE_SYN_MAX && !rc; ++r) {
+    if (!has_r[r]) continue;
+    cec::launch_syn(lp, r, false, shard_len, vec_ok, st);
+    rc = check_launch();
+  }
+  if (!rc) {
+    cec::launch_locate_plan(lp, shard_len, st);
+    rc = check_launch();
+  }
+  for (int r = 2; r <= CEC_LOCATE_SYN_MAX && !rc; ++r) {
+    if (!has_r[r]) continue;
+    cec::launch_syn(lp, r, true, shard_len, vec_ok, st);
+    rc = check_launch();
+  }
+  if (!rc) {
+    cec::launch_locate_finish(lp, st);
+    rc = check_launch();
+  }
+  return retire_behind(c, d, bytes, st, rc);
+}
+
+int cec_locate_ptrs(cec_codec* c, const uint8_t* const* shards, size_t nseg, size_t shard_len,
+                    int nsyn, uint8_t* d_flags, uint8_t* d_status, void* hip_stream) {
+  if (!c || (nseg && (!shards || !d_flags || !d_status))) return set_err(CEC_EINVAL, "null");
+  if (int rc = check_locate(c->k, c->m, nsyn)) return rc;
+  if (int rc = check_batch(nseg, shard_len)) return rc;
+  if (nseg == 0) return CEC_OK;
+  CEC_HIP_TRY(hipSetDevice(c->device));
+  return locate_impl(c, shards, nseg, shard_len, nsyn, d_flags, d_status,
+                     pick_stream(c, hip_stream));
 }
 
 int cec_reconstruct_partial_batch(cec_codec* c, uint8_t* d_data, uint8_t* d_parity, size_t nseg,

@@ -229,6 +229,36 @@ void launch_read_plan(const ReadPlan& p, bool rs21, hipStream_t st);
 void launch_read_copy(const uint64_t* tab, uint64_t nrows, uint64_t len, bool vec_ok,
                       hipStream_t st);
 
+// The corrupt shard found from parity alone (cec_locate_ptrs; the rule is locate_rule.h's). The
+// host knows every held set (the NULL pattern), so it uploads per distinct set one program chunk
+// of the syndrome product (r outputs from the h held shards in index order) and one planner table
+// (locate_rule.h loc_put_set), and per segment one row; nothing is written on the device but the
+// results and the four small arrays below.
+struct LocatePlan {
+  const uint64_t* rows;  // [nseg][rs]: {the set's chunk (0: h <= k, unchecked), the held addresses
+                         // in index order, ..., the set's index in word rs - 1}: TableAddr's view
+  const uint8_t* sets;   // [set][set_bytes]
+  uint64_t* witness;     // [nseg], preset to all ones: the lowest byte offset with S_0 != 0
+  uint32_t* cand;        // [nseg]: the candidate shard, or 0xFFFFFFFF (written for every segment)
+  uint8_t* dirty;        // [nseg], preset to 0: 1 where some syndrome byte is not zero
+  uint8_t* dirty2;       // [nseg], preset to 0: 1 where some T byte is not zero for the candidate
+  uint8_t* flags;        // [nseg][n], any alignment, written whole
+  uint8_t* status;       // [nseg]: kLoc* per segment
+  uint32_t rs, set_bytes;
+  uint32_t nseg;
+  int n, k;
+};
+// The syndrome product k_syn over all rows, for the rows whose chunk is of bucket `nob` (1..4;
+// every other row is left after its chunk's header, an unchecked one before it). confirm false:
+// the locate pass (dirty, witness). confirm true (nob >= 2): only rows with a candidate go on, and
+// dirty2 is what they write. Nothing else is stored.
+void launch_syn(const LocatePlan& p, int nob, bool confirm, uint64_t len, bool vec_ok,
+                hipStream_t st);
+// One wave per segment: the candidate from the shard bytes at the witness offset.
+void launch_locate_plan(const LocatePlan& p, uint64_t len, hipStream_t st);
+// One wave per segment: status and the n flag bytes.
+void launch_locate_finish(const LocatePlan& p, hipStream_t st);
+
 // SHA-256 of `n` equal-length buffers, written as 64 lowercase hex characters each into
 // `hex_out` (device, n * 64 bytes). If `ptrs` is null, buffer i is shard (i % nshards) of
 // segment (i / nshards) in layout L.

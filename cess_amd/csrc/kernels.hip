@@ -24,6 +24,7 @@
 #include "dev_util.h"
 #include "flag_solve.h"
 #include "read_plan.h"
+#include "locate_rule.h"
 #include "gf256.h"
 #include "hashq_where.h"
 #include "kernels.h"
@@ -2273,6 +2274,235 @@ void launch_confirm_flagged(const uint8_t* status, const uint8_t* ok, uint64_t n
   if (nseg == 0) return;
   hipLaunchKernelGGL(k_confirm_flagged, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, st,
                      status, ok, nseg, n, confirm);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The corrupt shard from parity alone (cec_locate_ptrs; locate_rule.h states the rule, kernels.h
+// LocatePlan the tables). The hot path is k_syn: k_ptrb's product with the r syndromes of a held
+// set as its outputs, which are tested for zero and never stored. Locate pass, planner, confirm
+// pass, finish, in that order on one stream; the four small arrays between them are indexed by
+// segment and every value in them is the same whatever order the waves ran in (a constant byte, a
+// minimum).
+// ---------------------------------------------------------------------------------------------
+static_assert(kLocateSynMax == 4, "one k_syn per bucket of the bit-plane product");
+
+// the lowest non-zero byte of a column (little-endian: the lowest address), its width for none
+__device__ __forceinline__ uint32_t first_nz_byte(uint32_t w) {
+  return w ? (uint32_t)__builtin_ctz(w) >> 3 : 4u;
+}
+__device__ __forceinline__ uint32_t first_nz_byte(u32x2 w) {
+  return w.x ? first_nz_byte(w.x) : 4u + first_nz_byte(w.y);
+}
+__device__ __forceinline__ uint32_t first_nz_byte(u32x4 w) {
+  return (w.x | w.y) ? first_nz_byte(u32x2{w.x, w.y}) : 8u + first_nz_byte(u32x2{w.z, w.w});
+}
+
+// j * x on packed bytes for a wave-uniform run-time j: the xtime powers of x, each XORed in under
+// the mask of its bit of j (an SGPR), as one column of the products above.
+template <class T>
+__device__ __forceinline__ T mul_uniform(uint32_t j, T x) {
+  T acc = T(0);
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    acc = bitop3_xand(acc, x, 0u - ((j >> b) & 1u));
+    if (b < 7) x = xt(x);
+  }
+  return acc;
+}
+
+// One workgroup of the syndrome product over the table row `a` (rtb_body's fold and Horner; the
+// byte tail goes to the last block, a call that is not vec_ok runs wholly byte-wise). `flag` is
+// the segment's byte of dirty (locate pass) or dirty2 (confirm pass): a plain store of 1 behind a
+// branch, the same value from every lane, as CmpSink::flush stores its 0. Locate pass: a wave's
+// lanes hold ascending offsets, so its lowest offset with S_0 != 0 is in the first lane that has
+// one, and that lane alone lowers the segment's witness: one 64-bit atomic min per wave and pass
+// at the most, however much of the fragment is bad. Confirm pass: T_a = S_{a+1} ^ j S_a for the
+// segment's candidate j.
+template <int NOB, class TV, int PF, bool CONFIRM>
+__device__ __forceinline__ void syn_body(const TableAddr& a, int vec_ok, uint32_t j, gu8* flag,
+                                         unsigned long long* wit) {
+  const cu32* __restrict__ P = a.P;
+  const uint32_t nin = P[0];
+  const uint64_t len = a.len();
+  const cu32* __restrict__ masks = P + kRtHeaderWords;
+  auto fold = [&]<class T>(T (&t)[NOB][8], auto ld) CEC_AI {
+    T ring[PF];
+#pragma unroll
+    for (int q = 0; q < PF; ++q)
+      if (q < (int)nin) ring[q] = ld(a.key((uint64_t)q));
+    for (uint32_t j0 = 0; j0 < nin; j0 += PF) {
+#pragma unroll
+      for (int q = 0; q < PF; ++q) {
+        const uint32_t i = j0 + q;
+        if (i >= nin) break;  // wave-uniform
+        const T cur = ring[q];
+        if (i + PF < nin) ring[q] = ld(a.key((uint64_t)(i + PF)));
+        const cu32* __restrict__ mk = masks + i * 8 * NOB;
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+#pragma unroll
+          for (int o = 0; o < NOB; ++o) t[o][b] = bitop3_xand(t[o][b], cur, mk[b * NOB + o]);
+      }
+    }
+  };
+  // the syndromes of a lane's column, which starts at byte offset `off`, and what they say
+  auto judge = [&]<class T>(const T (&t)[NOB][8], uint64_t off) CEC_AI {
+    T S[NOB];
+#pragma unroll
+    for (int o = 0; o < NOB; ++o) {
+      T r = t[o][7];
+#pragma unroll
+      for (int b = 6; b >= 0; --b) r = xt(r) ^ t[o][b];
+      S[o] = r;
+    }
+    uint32_t nz = 0;
+    if constexpr (!CONFIRM) {
+#pragma unroll
+      for (int o = 0; o < NOB; ++o) nz |= any_bits(S[o]);
+      if (nz) *flag = 1;
+      const unsigned long long m = __ballot(any_bits(S[0]) != 0);
+      if (m && (threadIdx.x & 63) == (uint32_t)__ffsll(m) - 1)
+        atomicMin(wit, (unsigned long long)(off + first_nz_byte(S[0])));
+    } else {
+#pragma unroll
+      for (int o = 0; o + 1 < NOB; ++o) nz |= any_bits(S[o + 1] ^ mul_uniform(j, S[o]));
+      if (nz) *flag = 1;
+    }
+  };
+  constexpr int VB = sizeof(TV);
+  if (vec_ok) {
+    const uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v < len / VB) {
+      TV t[NOB][8];
+#pragma unroll
+      for (int o = 0; o < NOB; ++o)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) t[o][b] = TV(0);
+      fold(t, [&](uint32_t key) CEC_AI { return ldv<true, TV>(a.in(key) + v * VB); });
+      judge(t, v * VB);
+    }
+    if (!(len % VB) || blockIdx.x != gridDim.x - 1) return;
+  }
+  // byte path: whole shard (vec_ok == 0, grid covers len) or the tail (last block)
+  const uint64_t i = vec_ok ? (len - len % VB) + threadIdx.x
+                            : (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= len) return;
+  uint32_t t[NOB][8];
+#pragma unroll
+  for (int o = 0; o < NOB; ++o)
+#pragma unroll
+    for (int b = 0; b < 8; ++b) t[o][b] = 0;
+  fold(t, [&](uint32_t key) CEC_AI -> uint32_t { return a.in(key)[i]; });
+  judge(t, i);
+}
+
+// Rows of all the call's segments, `rs` words apart. A confirm pass first loads the segment's
+// candidate, one scalar load, and "none" ends the workgroup there (the idle-row exit of
+// k_ptrb_flag); a row without a chunk (h <= k, unchecked) ends it before any address is formed,
+// and a row whose chunk is of another bucket belongs to another grid of the call.
+template <int NOB, class TV, int PF, bool CONFIRM>
+__global__ __launch_bounds__(256) void k_syn(const uint64_t* __restrict__ tab, uint32_t row0,
+                                             uint32_t rs, uint64_t len, int vec_ok,
+                                             uint8_t* __restrict__ flags,
+                                             uint64_t* __restrict__ witness,
+                                             const uint32_t* __restrict__ cand) {
+  const uint64_t r = row0 + blockIdx.y;
+  uint32_t j = 0;
+  if constexpr (CONFIRM) {
+    j = as_const(cand)[r];
+    if (j == kLocNone) return;
+  }
+  if (tab_row(tab, r, rs)[0] == 0) return;
+  const TableAddr a(tab, r, rs, len);
+  if (a.P[2] != (uint32_t)NOB) return;
+  syn_body<NOB, TV, PF, CONFIRM>(a, vec_ok, j, gptr((uint64_t)(uintptr_t)flags) + r,
+                                 (unsigned long long*)(witness + r));
+}
+
+// The candidate of a dirty segment: one wave per segment, four per workgroup. The lanes stride
+// over the held shards (n may exceed 64), load one byte each at the witness offset and multiply
+// it by the set's coefficient rows 0 and 1; an XOR reduction across the wave gives S_0 and S_1,
+// then every held lane tests S_1 == i * S_0 and the ballots must name exactly one.
+__global__ __launch_bounds__(256) void k_locate_plan(LocatePlan p, uint64_t len) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t s = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= p.nseg) return;  // the whole wave
+  const uint64_t* __restrict__ row = p.rows + s * p.rs;
+  const uint64_t x = p.witness[s];
+  uint32_t cand = kLocNone;
+  if (row[0] != 0 && p.dirty[s] != 0 && x < len) {  // wave-uniform; no witness is all ones
+    const uint8_t* __restrict__ set = p.sets + row[p.rs - 1] * p.set_bytes;
+    const uint32_t h = loc_set_h(set), n = (uint32_t)p.n;
+    if (loc_set_r(set) >= 2) {
+      const uint8_t* __restrict__ idx = set + kLocSetHead;
+      const uint8_t* __restrict__ c0 = idx + n;
+      const uint8_t* __restrict__ c1 = c0 + n;
+      uint32_t s0 = 0, s1 = 0;
+      for (uint32_t t = lane; t < h; t += 64) {
+        const uint32_t v = gptr(row[1 + t])[x];
+        s0 ^= fs_mul(c0[t], v);
+        s1 ^= fs_mul(c1[t], v);
+      }
+#pragma unroll
+      for (int d = 32; d; d >>= 1) {
+        s0 ^= (uint32_t)__shfl_xor((int)s0, d);
+        s1 ^= (uint32_t)__shfl_xor((int)s1, d);
+      }
+      uint32_t hits = 0;
+      for (uint32_t base = 0; base < h; base += 64) {
+        const uint32_t t = base + lane;
+        const unsigned long long m = __ballot(t < h && loc_matches(idx[t < h ? t : 0], s0, s1));
+        if (m) cand = idx[base + (uint32_t)__ffsll(m) - 1];
+        hits += (uint32_t)__popcll(m);
+      }
+      if (hits != 1) cand = kLocNone;
+    }
+  }
+  if (lane == 0) p.cand[s] = cand;
+}
+
+// Status and flags of every segment by loc_status and loc_flag: one wave per segment, the lanes
+// stride over its n flag bytes.
+__global__ __launch_bounds__(256) void k_locate_finish(LocatePlan p) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t s = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= p.nseg) return;  // the whole wave
+  const uint32_t n = (uint32_t)p.n;
+  const uint8_t* __restrict__ set = p.sets + p.rows[s * p.rs + p.rs - 1] * p.set_bytes;
+  const uint32_t cand = p.cand[s];
+  const uint32_t st = loc_status(loc_set_h(set), (uint32_t)p.k, loc_set_r(set), p.dirty[s] != 0,
+                                 cand, p.dirty2[s] != 0);
+  if (lane == 0) p.status[s] = (uint8_t)st;
+  const uint8_t* __restrict__ pos = set + kLocSetHead + 3 * n;
+  uint8_t* __restrict__ fl = p.flags + s * n;
+  for (uint32_t i = lane; i < n; i += 64) fl[i] = (uint8_t)loc_flag(st, pos[i] != 0, i, cand);
+}
+
+void launch_syn(const LocatePlan& p, int nob, bool confirm, uint64_t len, bool vec_ok,
+                hipStream_t st) {
+  if (p.nseg == 0 || (confirm && nob < 2)) return;
+  const int v = vec_ok ? 1 : 0;
+  rtb_dispatch(nob, [&]<int NOB, class TV, int PF>(RtbShape<NOB, TV, PF>) {
+    const unsigned gx = rt_grid_x(len, sizeof(TV), 1, vec_ok);
+    if (!confirm)
+      launch_rows(k_syn<NOB, TV, PF, false>, gx, p.rows, p.nseg, st, p.rs, len, v, p.dirty,
+                  p.witness, (const uint32_t*)p.cand);
+    else if constexpr (NOB >= 2)
+      launch_rows(k_syn<NOB, TV, PF, true>, gx, p.rows, p.nseg, st, p.rs, len, v, p.dirty2,
+                  p.witness, (const uint32_t*)p.cand);
+  });
+}
+
+void launch_locate_plan(const LocatePlan& p, uint64_t len, hipStream_t st) {
+  if (p.nseg == 0) return;
+  hipLaunchKernelGGL(k_locate_plan, dim3((unsigned)(((uint64_t)p.nseg + 3) / 4)), dim3(256), 0, st,
+                     p, len);
+}
+
+void launch_locate_finish(const LocatePlan& p, hipStream_t st) {
+  if (p.nseg == 0) return;
+  hipLaunchKernelGGL(k_locate_finish, dim3((unsigned)(((uint64_t)p.nseg + 3) / 4)), dim3(256), 0,
+                     st, p);
 }
 
 }  // namespace cec

@@ -623,6 +623,56 @@ class Encoder:
         check(rc, "ReadFlaggedDevice")
         return d_status
 
+    def LocateDevice(self, segments: Sequence, nsyn: int = _lib.CEC_LOCATE_SYN_MAX, d_flags=None,
+                     d_status=None, stream=None):
+        """Find the corrupt fragment of every segment from parity alone (cec_locate_ptrs), no
+        hash involved: `segments` is a list of lists of k + m 1-D uint8 device tensors (None = not
+        held), which are only read. With h shards held and r = min(nsyn, h - k) checks, a segment
+        is CEC_LOCATE_CLEAN (the held shards agree), FOUND (exactly one held shard disagrees with
+        the others; its flag is 0, the other held flags 1), AMBIGUOUS (inconsistent, but no single
+        shard explains it, or r == 1: every held flag 0) or UNCHECKED (h <= k: nothing to check
+        with, held flags 1). locate_host states the rule. Returns (d_flags uint8 [nseg, k + m],
+        d_status uint8 [nseg]), the given tensors or new ones; d_flags is what
+        RepairFlaggedDevice, RepairFlaggedMultiDevice, ReadFlaggedDevice and
+        HashQueue.add_check_where_ptrs consume. Every tensor must be contiguous and on the codec's
+        GPU (TypeError for a shard, ErrInvalidInput for `d_flags` / `d_status` and for `nsyn`
+        outside 1..CEC_LOCATE_SYN_MAX). Enqueued on `stream` (default: torch's current stream) and
+        not waited for; nothing is copied to the host."""
+        import torch
+        if not 1 <= int(nsyn) <= _lib.CEC_LOCATE_SYN_MAX:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        nseg, n = len(segments), self.Shards
+        dev = torch.device("cuda", self.device)
+        if d_flags is None:
+            d_flags = torch.empty((nseg, n), dtype=torch.uint8, device=dev)
+        elif (d_flags.dtype != torch.uint8 or d_flags.numel() != nseg * n or d_flags.device != dev
+              or not d_flags.is_contiguous()):
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        if d_status is None:
+            d_status = torch.empty(nseg, dtype=torch.uint8, device=dev)
+        elif (d_status.dtype != torch.uint8 or d_status.dim() != 1 or d_status.numel() != nseg
+              or d_status.device != dev or not d_status.is_contiguous()):
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        if nseg == 0:
+            return d_flags, d_status
+        if self.ParityShards == 0:  # no parity, no check
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        ptrs = (c_void_p * (nseg * n))()
+        held = []
+        for s, shards in enumerate(segments):
+            if len(shards) != n:
+                raise ErrTooFewShards(ErrTooFewShards.__doc__)
+            for i, t in enumerate(shards):
+                if t is None:
+                    continue
+                held.append(_on_gpu(t, dev))
+                ptrs[s * n + i] = _dev_ptr(t)
+        size = self._check_device_shards(held) if held else 1
+        check(self._lib.cec_locate_ptrs(self._h, ptrs, nseg, size, int(nsyn), _dev_ptr(d_flags),
+                                        _dev_ptr(d_status), self._device_stream(stream)),
+              "LocateDevice")
+        return d_flags, d_status
+
     def ReconstructPartialDevice(self, shards: Sequence, present, out=None,
                                  accumulate: bool = False, stream=None) -> dict:
         """Partial rebuild of one segment in place (cec_reconstruct_partial_ptrs). `shards` is a
@@ -1063,6 +1113,43 @@ def read_status(data_shards: int, parity_shards: int, held, flags, wanted, max_b
                                       f.ctypes.data_as(u8p), w.ctypes.data_as(u8p), max_bad,
                                       byref(status), byref(nmiss), miss), "read_status")
     return status.value, [int(x) for x in miss[:nmiss.value]]
+
+
+def locate_rows(data_shards: int, parity_shards: int, held, nsyn: int):
+    """Host only (cec_locate_rows): the check rows of a held set. `held` is k+m values. Returns
+    (r, rows): r = min(nsyn, h - k) checks (0 when h <= k) and rows uint8 [r][k+m] with
+    rows[a][i] = u_i * i^a for held i, 0 elsewhere; every row XOR-multiplied into the held shards
+    of a consistent segment gives zero at every byte."""
+    n = data_shards + parity_shards
+    h = np.ascontiguousarray(np.asarray(held, dtype=np.uint8))
+    if h.shape != (n,):
+        raise ValueError("held must have k+m values")
+    r = c_int(-1)
+    rows = np.zeros((_lib.CEC_LOCATE_SYN_MAX, n), np.uint8)
+    u8p = POINTER(c_uint8)
+    check(_lib.load().cec_locate_rows(data_shards, parity_shards, h.ctypes.data_as(u8p), nsyn,
+                                      byref(r), rows.ctypes.data_as(u8p)), "locate_rows")
+    return r.value, rows[:r.value].copy()
+
+
+def locate_host(data_shards: int, parity_shards: int, shards, nsyn: int):
+    """Host only (cec_locate_host): the rule Encoder.LocateDevice applies to one segment on the
+    GPU, on host memory. `shards` is k+m buffers of one length, None = not held. Returns
+    (CEC_LOCATE_* status, the shard of a FOUND segment or -1)."""
+    n = data_shards + parity_shards
+    if len(shards) != n:
+        raise ValueError("shards must have k+m entries")
+    arrs = [None if s is None else np.frombuffer(s, np.uint8) if isinstance(s, bytes)
+            else _as_u8(s) for s in shards]
+    sizes = {a.size for a in arrs if a is not None}
+    if len(sizes) > 1:
+        raise ErrShardSize(ErrShardSize.__doc__)
+    ptrs = (c_void_p * n)(*[None if a is None else a.ctypes.data for a in arrs])
+    status, found = c_int(-1), c_int(-2)
+    check(_lib.load().cec_locate_host(data_shards, parity_shards, ptrs,
+                                      sizes.pop() if sizes else 0, nsyn, byref(status),
+                                      byref(found)), "locate_host")
+    return status.value, found.value
 
 
 def confirm_rule(status: int, ok) -> int:

@@ -472,6 +472,77 @@ int cec_confirm_rule(int n, int status, const uint8_t* ok, int* confirm);
  *    d_confirm, or a NULL d_ok with n > 0; nseg >= 2^33. nseg == 0: CEC_OK. */
 int cec_confirm_flagged(const uint8_t* d_status, const uint8_t* d_ok, size_t nseg, int n,
                         uint8_t* d_confirm, void* hip_stream);
+/* ---- the corrupt fragment found from parity alone ----------------------------------------------
+ * The flags the calls above consume have had one source, a hash of every held fragment. For every
+ * held set with two or more shards of redundancy the parity already names a single bad shard: in
+ * this codec's convention shard i is f(i) for one polynomial f of degree < k, so the h held shards
+ * of a segment, at the points H, satisfy at every byte offset
+ *   S_a = XOR_{i in H} u_i * i^a * v_i = 0     a = 0 .. h-k-1
+ *   u_i = 1 / prod_{i' in H, i' != i} (i ^ i')   (0^0 = 1)
+ * and one bad shard j with error e gives S_a = u_j j^a e: S_1 = j S_0. With j known, T_a =
+ * S_{a+1} ^ j S_a are the checks of the held set without j.
+ * The rule, per segment, with r = min(nsyn, h - k) and nsyn in [1, CEC_LOCATE_SYN_MAX]: */
+#define CEC_LOCATE_SYN_MAX 4
+#define CEC_LOCATE_CLEAN 0     /* r >= 1 and S_0..S_{r-1} zero at every byte offset: held flags 1 */
+#define CEC_LOCATE_FOUND 1     /* dirty, r >= 2, and: some byte offset has S_0 != 0; at the lowest
+                                  such offset x exactly one j in H has S_1(x) = j S_0(x); T_0 ..
+                                  T_{r-2} for that j are zero at every byte offset: held flags 1,
+                                  shard j 0 */
+#define CEC_LOCATE_AMBIGUOUS 2 /* dirty and not FOUND, every dirty segment with r = 1 included:
+                                  held flags 0 */
+#define CEC_LOCATE_UNCHECKED 3 /* h <= k: no redundancy is held, no shard byte is read: held
+                                  flags 1 */
+/* Flag bytes of shards that are not held are written 0; every reader ignores them. AMBIGUOUS marks
+ * every held shard bad on purpose: the flagged repairs then report CEC_FLAG_LOST and write
+ * nothing, cec_read_flagged_ptrs refuses the inconsistent segment, and
+ * cec_hashq_add_check_where_ptrs with gate = CEC_LOCATE_AMBIGUOUS hashes exactly those fragments.
+ * The guarantee and its limit: if exactly one held shard of a segment differs from the codeword of
+ * the others, the segment is FOUND with that shard, for any r >= 2. If b held shards differ, 2 <=
+ * b <= r - 1, the segment is never FOUND. With b >= r a wrong FOUND is possible (errors in several
+ * shards at the same byte offsets can imitate one), which is what cec_confirm_flagged is for. The
+ * rule is a statement about the mutual consistency of the held shards, not about their recorded
+ * hashes.
+ * Host only: the check rows of a held set. held: k+m bytes; *r receives min(nsyn, h - k) (0 for
+ * h <= k); rows (CEC_LOCATE_SYN_MAX*(k+m) bytes, written whole): rows[a*(k+m) + i] = u_i * i^a for
+ * held i and a < *r, and 0 elsewhere. CEC_EINVAL: a NULL pointer, nsyn out of range, k, m out of
+ * the codec's range. */
+int cec_locate_rows(int k, int m, const uint8_t* held, int nsyn, int* r, uint8_t* rows);
+/* Host only: the rule on host memory, by the device code's own functions (csrc/locate_rule.h) with
+ * loops in place of lanes. shards: k+m HOST pointers to shard_len bytes each, NULL = not held.
+ * *status receives the CEC_LOCATE_* code, *found the shard of a FOUND segment, else -1. Refusals
+ * as above. */
+int cec_locate_host(int k, int m, const uint8_t* const* shards, size_t shard_len, int nsyn,
+                    int* status, int* found);
+/* The call. shards as in cec_repair_flagged_ptrs, read-only: a HOST array of nseg*n DEVICE
+ * pointers (n = k+m), NULL = not held. d_flags: nseg*n DEVICE bytes at any alignment, written
+ * whole, in the layout the repairs, the read and the where-add consume. d_status: nseg DEVICE
+ * bytes, one CEC_LOCATE_* code per segment.
+ *  - Reads: the held shards of segments with h > k, once; those of dirty segments with a
+ *    candidate once more. Nothing of an UNCHECKED segment is read.
+ *  - Writes: d_flags and d_status and nothing else. No shard is written.
+ *  - Not waited for: everything is enqueued on hip_stream, nothing is copied to the host. (It
+ *    waits for the codec's own upload stream, for its table, as the other _ptrs calls do.)
+ *  - Validation: before anything is enqueued; an error writes no byte. CEC_EINVAL: a NULL codec;
+ *    with nseg > 0 a NULL shards, d_flags or d_status; nsyn outside [1, CEC_LOCATE_SYN_MAX].
+ *    CEC_ESHARDLEN: shard_len == 0. nseg == 0: CEC_OK. Shard addresses may alias: they are only
+ *    read.
+ *  - Alignment: any; 16-byte-aligned held addresses give vector columns with a byte tail,
+ *    otherwise the whole call runs byte-wise.
+ *  - Memory: one block from the codec's pool, retired behind the launches (CEC_STAT_POOL_BYTES
+ *    does not grow across repeated calls): per segment a row of 8(most + 2) bytes, most being the
+ *    largest held set, and 14 bytes of state; per distinct held set a planner table of 4n + 8
+ *    bytes and one program chunk of 4(772 + 8hr) bytes. The decode cache is neither read nor
+ *    filled (CEC_STAT_DECODE_CACHED does not change).
+ *  - HIP graph capture: not capturable, for the reasons given at cec_reconstruct_ptrs (the
+ *    kernels read a codec-owned table that is retired once the launches complete).
+ * One grid of the syndrome product per value of r in the call, over all rows (a row of another r
+ * or without redundancy is left after one or two scalar loads); a planner wave per segment reads
+ * one byte of each held shard at the witness offset, the lowest offset with S_0 != 0 (a minimum,
+ * so the result does not depend on the order in which waves ran); the confirm grids run where
+ * there is a candidate; a last kernel writes status and flags. Not covered: two or more bad
+ * shards per segment (they are AMBIGUOUS for up to r - 1 of them), shards in the batch layout. */
+int cec_locate_ptrs(cec_codec* codec, const uint8_t* const* shards, size_t nseg, size_t shard_len,
+                    int nsyn, uint8_t* d_flags, uint8_t* d_status, void* hip_stream);
 /* ---- parity accumulated shard by shard (klauspost EncodeIdx and Update) -----------------------
  * Both are one primitive on the codec's encode matrix E (cec_matrix; row k+o is parity shard o):
  *   parity[o] ^= E[k+o][j] * x_j   for every o < m,

@@ -211,6 +211,13 @@ pub mod sys {
                                      d_flags: *const u8, dst: *const *mut u8, nseg: usize,
                                      shard_len: usize, max_bad: c_int, d_status: *mut u8,
                                      stream: *mut c_void) -> c_int;
+        pub fn cec_locate_rows(k: c_int, m: c_int, held: *const u8, nsyn: c_int, r: *mut c_int,
+                               rows: *mut u8) -> c_int;
+        pub fn cec_locate_host(k: c_int, m: c_int, shards: *const *const u8, shard_len: usize,
+                               nsyn: c_int, status: *mut c_int, found: *mut c_int) -> c_int;
+        pub fn cec_locate_ptrs(c: *mut cec_codec, shards: *const *const u8, nseg: usize,
+                               shard_len: usize, nsyn: c_int, d_flags: *mut u8,
+                               d_status: *mut u8, stream: *mut c_void) -> c_int;
         pub fn cec_encode_idx_batch(c: *mut cec_codec, d_shard: *const u8,
                                     shard_seg_stride: usize, idx: c_int, d_parity: *mut u8,
                                     nseg: usize, shard_len: usize, accumulate: c_int,
@@ -438,6 +445,11 @@ pub const CEC_FLAG_REBUILT: c_int = 1;
 pub const CEC_FLAG_MANY: c_int = 2;
 pub const CEC_FLAG_LOST: c_int = 3;
 pub const CEC_FLAG_MULTI_MAX: c_int = 4;
+pub const CEC_LOCATE_SYN_MAX: c_int = 4;
+pub const CEC_LOCATE_CLEAN: c_int = 0;
+pub const CEC_LOCATE_FOUND: c_int = 1;
+pub const CEC_LOCATE_AMBIGUOUS: c_int = 2;
+pub const CEC_LOCATE_UNCHECKED: c_int = 3;
 pub const CEC_CONFIRM_NONE: c_int = 0;
 pub const CEC_CONFIRM_PROVEN: c_int = 1;
 pub const CEC_CONFIRM_REFUTED: c_int = 2;
@@ -810,6 +822,67 @@ impl ReedSolomon {
                             miss.as_mut_ptr())
         })?;
         Ok((status, miss[..nmiss as usize].iter().map(|&i| i as usize).collect()))
+    }
+
+    /// Find the corrupt shard of every segment from parity alone (`cec_locate_ptrs`): `shards`
+    /// holds `nseg * (k + m)` device addresses, segment by segment, null = not held; they are only
+    /// read. `d_status` receives one `CEC_LOCATE_*` code per segment and `d_flags` one byte per
+    /// shard in the layout the flagged repairs and the flagged read consume: 1 for a held shard
+    /// that is consistent, 0 for the one shard of a `CEC_LOCATE_FOUND` segment that disagrees with
+    /// the others and for every shard of a `CEC_LOCATE_AMBIGUOUS` one (`locate_host` states the
+    /// rule). `nsyn` in `1..=CEC_LOCATE_SYN_MAX` bounds the checks per byte. Enqueued on `stream`
+    /// and not waited for; nothing is copied to the host.
+    ///
+    /// # Safety
+    /// Every non-null entry of `shards` must be valid device memory of `shard_len` bytes,
+    /// `d_flags` of `shards.len()` bytes and `d_status` of one byte per segment, all until the
+    /// work enqueued on `stream` has run.
+    pub unsafe fn locate_ptrs(&self, shards: &[*const u8], shard_len: usize, nsyn: i32,
+                              d_flags: *mut u8, d_status: *mut u8,
+                              stream: *mut c_void) -> Result<(), Error> {
+        let n = self.k + self.m;
+        if shards.len() % n != 0 {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        check(cec_locate_ptrs(self.c, shards.as_ptr(), shards.len() / n, shard_len,
+                              nsyn as c_int, d_flags, d_status, stream))
+    }
+
+    /// The check rows of a held set (`cec_locate_rows`, host only): returns r = min(nsyn, h - k)
+    /// and r rows of k + m coefficients, `rows[a][i]` = u_i * i^a for held i and 0 elsewhere; each
+    /// row applied to the held shards of a consistent segment gives zero at every byte.
+    pub fn locate_rows(&self, held: &[u8], nsyn: i32) -> Result<(usize, Vec<Vec<u8>>), Error> {
+        let n = self.k + self.m;
+        if held.len() != n {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        let mut r: c_int = 0;
+        let mut rows = vec![0u8; CEC_LOCATE_SYN_MAX as usize * n];
+        check(unsafe {
+            cec_locate_rows(self.k as c_int, self.m as c_int, held.as_ptr(), nsyn as c_int,
+                            &mut r, rows.as_mut_ptr())
+        })?;
+        Ok((r as usize, rows.chunks(n).take(r as usize).map(|c| c.to_vec()).collect()))
+    }
+
+    /// The rule `locate_ptrs` applies to one segment, on host memory (`cec_locate_host`):
+    /// `shards` holds k + m entries of one length, `None` = not held. Returns the `CEC_LOCATE_*`
+    /// status and the shard of a `CEC_LOCATE_FOUND` segment.
+    pub fn locate_host(&self, shards: &[Option<&[u8]>],
+                       nsyn: i32) -> Result<(i32, Option<usize>), Error> {
+        let n = self.k + self.m;
+        let len = shards.iter().flatten().map(|s| s.len()).next().unwrap_or(0);
+        if shards.len() != n || shards.iter().flatten().any(|s| s.len() != len) {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        let ptrs: Vec<*const u8> =
+            shards.iter().map(|s| s.map_or(std::ptr::null(), |b| b.as_ptr())).collect();
+        let (mut status, mut found): (c_int, c_int) = (0, -1);
+        check(unsafe {
+            cec_locate_host(self.k as c_int, self.m as c_int, ptrs.as_ptr(), len, nsyn as c_int,
+                            &mut status, &mut found)
+        })?;
+        Ok((status, if found >= 0 { Some(found as usize) } else { None }))
     }
 
     /// EncodeIdx on scattered device shards in place (`cec_encode_idx_ptrs`): `data` holds
