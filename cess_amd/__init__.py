@@ -16,6 +16,7 @@ from ._lib import (
     CEC_FLAG_REBUILT,
     CEC_HASHQ_SKIPPED,
     CEC_LOCATE_AMBIGUOUS,
+    CEC_LOCATE_BAD_MAX,
     CEC_LOCATE_CLEAN,
     CEC_LOCATE_FOUND,
     CEC_LOCATE_SYN_MAX,
@@ -43,6 +44,7 @@ from .reedsolomon import (
     flag_status,
     flag_status_multi,
     locate_host,
+    locate_multi_host,
     locate_rows,
     read_status,
     sha256_hex_device,
@@ -60,5 +62,5 @@ __all__ = [
     "confirm_flagged", "confirm_rule", "CEC_CONFIRM_NONE", "CEC_CONFIRM_PROVEN",
     "CEC_CONFIRM_REFUTED", "CEC_HASHQ_SKIPPED", "read_status",
     "locate_rows", "locate_host", "CEC_LOCATE_SYN_MAX", "CEC_LOCATE_CLEAN", "CEC_LOCATE_FOUND",
-    "CEC_LOCATE_AMBIGUOUS", "CEC_LOCATE_UNCHECKED",
+    "CEC_LOCATE_AMBIGUOUS", "CEC_LOCATE_UNCHECKED", "locate_multi_host", "CEC_LOCATE_BAD_MAX",
 ]

@@ -110,6 +110,10 @@ SIGNATURES = {
                                 POINTER(c_int)]),
     "cec_locate_ptrs": (c_int, [c_void_p, POINTER(c_void_p), c_size_t, c_size_t, c_int, c_void_p,
                                 c_void_p, c_void_p]),
+    "cec_locate_multi_host": (c_int, [c_int, c_int, POINTER(c_void_p), c_size_t, c_int, c_int,
+                                      POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "cec_locate_multi_ptrs": (c_int, [c_void_p, POINTER(c_void_p), c_size_t, c_size_t, c_int,
+                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cec_encode_idx_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_size_t,
                                      c_size_t, c_int, c_void_p]),
     "cec_update_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,
@@ -267,6 +271,7 @@ CEC_LOCATE_CLEAN = 0
 CEC_LOCATE_FOUND = 1
 CEC_LOCATE_AMBIGUOUS = 2
 CEC_LOCATE_UNCHECKED = 3
+CEC_LOCATE_BAD_MAX = 2
 CEC_CONFIRM_NONE = 0
 CEC_CONFIRM_PROVEN = 1
 CEC_CONFIRM_REFUTED = 2

@@ -339,6 +339,56 @@ def locate_repair_device(enc: Encoder, segments: Sequence, nsyn: int = _lib.CEC_
         return go(q)
 
 
+def locate_repair_multi_device(enc: Encoder, segments: Sequence,
+                               max_bad: int = _lib.CEC_LOCATE_BAD_MAX,
+                               nsyn: int = _lib.CEC_LOCATE_SYN_MAX, recorded=None, queue=None):
+    """locate_repair_device for up to `max_bad` bad fragments per segment:
+    Encoder.LocateMultiDevice names the one or two fragments of a segment that disagree with the
+    others, from parity alone, and Encoder.RepairFlaggedMultiDevice(..., max_bad=max_bad) reads
+    those flags on the same stream and rebuilds them in place. Arguments, streams and the proof
+    with `recorded` as in locate_repair_device. Returns (d_flags, d_locate, d_status), or with
+    `recorded` (d_flags, d_locate, d_status, d_ok, d_confirm). A FOUND segment is REBUILT; an
+    AMBIGUOUS one (three bad fragments, say) has every held flag 0, so the repair reports LOST and
+    writes nothing. Nothing is waited for."""
+    import torch
+    from .hashq import HashQueue
+    segments = [list(seg) for seg in segments]
+    nseg, n = len(segments), enc.Shards
+    if any(len(seg) != n for seg in segments):
+        raise ErrInvalidInput(ErrInvalidInput.__doc__)
+    dev = torch.device("cuda", enc.device)
+
+    def heal(stream):
+        d_flags, d_locate, _ = enc.LocateMultiDevice(segments, nsyn=nsyn, max_bad=max_bad,
+                                                     stream=stream)
+        return d_flags, d_locate, enc.RepairFlaggedMultiDevice(segments, d_flags,
+                                                               max_bad=max_bad, stream=stream)
+
+    if recorded is None:
+        return heal(torch.cuda.current_stream(dev) if queue is None else _queue_stream(queue)[0])
+    _, slots, rec, _, _ = _scrub_table(enc, segments, recorded)
+
+    def go(q):
+        stream = _queue_stream(q)[0]
+        d_flags, d_locate, d_status = heal(stream)
+        d_ok = torch.empty((nseg, n), dtype=torch.uint8, device=dev)
+        flat, ok = d_flags.view(-1), d_ok.view(-1)
+        step = max(1, q.capacity // n)  # whole segments per slice
+        for s0 in range(0, nseg, step):
+            s1 = min(nseg, s0 + step)
+            a, b = s0 * n, s1 * n
+            q.add_check_where_ptrs(slots[a:b], rec[a:b], flat[a:b], per=n, d_gate=d_status[s0:s1],
+                                   gate=_lib.CEC_FLAG_REBUILT, d_ok=ok[a:b])
+            q.finish()
+        return d_flags, d_locate, d_status, d_ok, confirm_flagged(d_status, d_ok, n, stream=stream)
+
+    if queue is not None:
+        return go(queue)
+    cap = 1 << max(0, nseg * n - 1).bit_length()
+    with HashQueue(capacity=cap, device=enc.device, stream=torch.cuda.current_stream(dev)) as q:
+        return go(q)
+
+
 def scrub_located_device(enc: Encoder, segments: Sequence, recorded,
                          nsyn: int = _lib.CEC_LOCATE_SYN_MAX, queue=None):
     """A scrub that hashes only what parity cannot settle, RS(2,1) included: Encoder.LocateDevice

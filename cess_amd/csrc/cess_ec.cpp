@@ -33,6 +33,7 @@
 #include "fftdec_plan.h"
 #include "flag_solve.h"
 #include "read_plan.h"
+#include "locate_multi_rule.h"
 #include "locate_rule.h"
 #include "gf256.h"
 #include "hashq_where.h"
@@ -2286,8 +2287,14 @@ int cec_locate_host(int k, int m, const uint8_t* const* shards, size_t shard_len
 // candidate, dirty, dirty2 per segment), preset on `st`. One grid of the syndrome product per
 // value of r in the call, the planner, the confirm grids, the finish. Nothing here waits for `st`
 // or copies from the device, and the decode cache is not touched.
+//
+// cec_locate_multi_ptrs with max_bad = 2 (`pair`) takes the same rows and chunks, the planner
+// tables with four coefficient rows, and two more arrays (the second witness, dirtyU): locate
+// pass, first solve, T confirm, second solve, U confirm, finish. Without `pair` the launches are
+// cec_locate_ptrs' own, and d_nbad, where given, is derived from the status they wrote.
 static int locate_impl(cec_codec* c, const uint8_t* const* shards, size_t nseg, size_t shard_len,
-                       int nsyn, uint8_t* d_flags, uint8_t* d_status, hipStream_t st) {
+                       int nsyn, bool pair, uint8_t* d_flags, uint8_t* d_status, uint8_t* d_nbad,
+                       hipStream_t st) {
   const uint32_t n = (uint32_t)(c->k + c->m), k = (uint32_t)c->k;
   struct Set {
     std::string key;
@@ -2318,7 +2325,7 @@ static int locate_impl(cec_codec* c, const uint8_t* const* shards, size_t nseg, 
     has_r[r] = true;
   }
   const bool vec_ok = (bits & 15) == 0;
-  const uint32_t rs = most + 2, set_bytes = cec::loc_set_bytes(n);
+  const uint32_t rs = most + 2, set_bytes = pair ? cec::loc2_set_bytes(n) : cec::loc_set_bytes(n);
   const size_t sets_at = nseg * rs;
   size_t in_words = sets_at + sets.size() * (set_bytes / 8);
   for (Set& g : sets) {
@@ -2326,8 +2333,10 @@ static int locate_impl(cec_codec* c, const uint8_t* const* shards, size_t nseg, 
     g.chunk_at = in_words;
     in_words += (cec::fs_chunk_words(g.h, g.r) + 1) / 2;
   }
-  const size_t wit_at = in_words, cand_at = wit_at + nseg, dirty_at = cand_at + (nseg + 1) / 2;
-  const size_t words = dirty_at + (2 * nseg + 7) / 8;
+  // witness (and the second one of the pair rule), candidate, then the dirty bytes
+  const size_t wit_at = in_words, cand_at = wit_at + (pair ? 2 : 1) * nseg;
+  const size_t dirty_at = cand_at + (nseg + 1) / 2, ndirty = (pair ? 3 : 2) * nseg;
+  const size_t words = dirty_at + (ndirty + 7) / 8;
   const size_t bytes = words * sizeof(uint64_t);
   void* d = nullptr;
   int rc = c->pool.alloc(bytes, &d);
@@ -2336,8 +2345,9 @@ static int locate_impl(cec_codec* c, const uint8_t* const* shards, size_t nseg, 
   std::vector<uint64_t> host(in_words, 0);
   for (size_t g = 0; g < sets.size(); ++g) {
     const Set& set = sets[g];
-    cec::loc_put_set(reinterpret_cast<uint8_t*>(host.data() + sets_at) + g * set_bytes,
-                     reinterpret_cast<const uint8_t*>(set.key.data()), n, set.r);
+    (pair ? cec::loc2_put_set : cec::loc_put_set)(
+        reinterpret_cast<uint8_t*>(host.data() + sets_at) + g * set_bytes,
+        reinterpret_cast<const uint8_t*>(set.key.data()), n, set.r);
     if (!set.r) continue;
     uint8_t H[cec::kMaxShards];
     uint32_t h = 0;
@@ -2359,6 +2369,57 @@ static int locate_impl(cec_codec* c, const uint8_t* const* shards, size_t nseg, 
   if (rc) {
     c->pool.retire(d, bytes);
     return rc;
+  }
+  if (pair) {
+    cec::PairPlan pp{};
+    pp.rows = dw;
+    pp.sets = reinterpret_cast<const uint8_t*>(dw + sets_at);
+    pp.witness = dw + wit_at;
+    pp.witness2 = pp.witness + nseg;
+    pp.cand = reinterpret_cast<uint32_t*>(dw + cand_at);
+    pp.dirty = reinterpret_cast<uint8_t*>(dw + dirty_at);
+    pp.dirtyT = pp.dirty + nseg;
+    pp.dirtyU = pp.dirtyT + nseg;
+    pp.flags = d_flags;
+    pp.status = d_status;
+    pp.nbad = d_nbad;
+    pp.rs = rs;
+    pp.set_bytes = set_bytes;
+    pp.nseg = (uint32_t)nseg;
+    pp.n = (int)n;
+    pp.k = (int)k;
+    pp.max_bad = CEC_LOCATE_BAD_MAX;
+    hipError_t e = hipMemsetAsync(pp.witness, 0xFF, 2 * nseg * sizeof(uint64_t), st);
+    if (e == hipSuccess) e = hipMemsetAsync(pp.dirty, 0, ndirty, st);
+    if (e != hipSuccess)
+      rc = set_err(CEC_EHIP, std::string("locate preset: ") + hipGetErrorString(e));
+    for (int r = 1; r <= CEC_LOCATE_SYN_MAX && !rc; ++r) {
+      if (!has_r[r]) continue;
+      cec::launch_pair_syn(pp, r, 0, shard_len, vec_ok, st);
+      rc = check_launch();
+    }
+    if (!rc) {
+      cec::launch_pair_plan(pp, shard_len, 0, st);
+      rc = check_launch();
+    }
+    for (int r = 2; r <= CEC_LOCATE_SYN_MAX && !rc; ++r) {
+      if (!has_r[r]) continue;
+      cec::launch_pair_syn(pp, r, 1, shard_len, vec_ok, st);
+      rc = check_launch();
+    }
+    if (has_r[4] && !rc) {
+      cec::launch_pair_plan(pp, shard_len, 1, st);
+      rc = check_launch();
+      if (!rc) {
+        cec::launch_pair_syn(pp, 4, 2, shard_len, vec_ok, st);
+        rc = check_launch();
+      }
+    }
+    if (!rc) {
+      cec::launch_pair_finish(pp, st);
+      rc = check_launch();
+    }
+    return retire_behind(c, d, bytes, st, rc);
   }
   cec::LocatePlan lp{};
   lp.rows = dw;
@@ -2395,6 +2456,10 @@ static int locate_impl(cec_codec* c, const uint8_t* const* shards, size_t nseg, 
     cec::launch_locate_finish(lp, st);
     rc = check_launch();
   }
+  if (!rc && d_nbad) {
+    cec::launch_pair_nbad_single(d_status, d_nbad, nseg, st);
+    rc = check_launch();
+  }
   return retire_behind(c, d, bytes, st, rc);
 }
 
@@ -2405,7 +2470,50 @@ int cec_locate_ptrs(cec_codec* c, const uint8_t* const* shards, size_t nseg, siz
   if (int rc = check_batch(nseg, shard_len)) return rc;
   if (nseg == 0) return CEC_OK;
   CEC_HIP_TRY(hipSetDevice(c->device));
-  return locate_impl(c, shards, nseg, shard_len, nsyn, d_flags, d_status,
+  return locate_impl(c, shards, nseg, shard_len, nsyn, false, d_flags, d_status, nullptr,
+                     pick_stream(c, hip_stream));
+}
+
+// ---- one or two corrupt shards from parity alone (locate_multi_rule.h) -------------------------
+
+static_assert(CEC_LOCATE_BAD_MAX == cec::kLocateBadMax, "locate_multi_rule.h states the rule");
+
+static int check_locate_multi(int k, int m, int nsyn, int max_bad) {
+  if (int rc = check_locate(k, m, nsyn)) return rc;
+  if (max_bad < 1 || max_bad > CEC_LOCATE_BAD_MAX)
+    return set_err(CEC_EINVAL, "max_bad must be 1..CEC_LOCATE_BAD_MAX");
+  return CEC_OK;
+}
+
+int cec_locate_multi_host(int k, int m, const uint8_t* const* shards, size_t shard_len, int nsyn,
+                          int max_bad, int* status, int* nfound, int found[2]) {
+  if (!shards || !status || !nfound || !found) return set_err(CEC_EINVAL, "null");
+  if (int rc = check_locate_multi(k, m, nsyn, max_bad)) return rc;
+  uint32_t st = 0;
+  if (max_bad == 1) {  // cec_locate_host's rule, its code
+    int one = -1;
+    cec::loc_segment_host((uint32_t)k, (uint32_t)(k + m), shards, shard_len, (uint32_t)nsyn, &st,
+                          &one);
+    *nfound = one >= 0 ? 1 : 0;
+    found[0] = one;
+    found[1] = -1;
+  } else {
+    cec::loc2_segment_host((uint32_t)k, (uint32_t)(k + m), shards, shard_len, (uint32_t)nsyn,
+                           (uint32_t)max_bad, &st, nfound, found);
+  }
+  *status = (int)st;
+  return CEC_OK;
+}
+
+int cec_locate_multi_ptrs(cec_codec* c, const uint8_t* const* shards, size_t nseg,
+                          size_t shard_len, int nsyn, int max_bad, uint8_t* d_flags,
+                          uint8_t* d_status, uint8_t* d_nbad, void* hip_stream) {
+  if (!c || (nseg && (!shards || !d_flags || !d_status))) return set_err(CEC_EINVAL, "null");
+  if (int rc = check_locate_multi(c->k, c->m, nsyn, max_bad)) return rc;
+  if (int rc = check_batch(nseg, shard_len)) return rc;
+  if (nseg == 0) return CEC_OK;
+  CEC_HIP_TRY(hipSetDevice(c->device));
+  return locate_impl(c, shards, nseg, shard_len, nsyn, max_bad >= 2, d_flags, d_status, d_nbad,
                      pick_stream(c, hip_stream));
 }
 

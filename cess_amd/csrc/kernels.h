@@ -259,6 +259,41 @@ void launch_locate_plan(const LocatePlan& p, uint64_t len, hipStream_t st);
 // One wave per segment: status and the n flag bytes.
 void launch_locate_finish(const LocatePlan& p, hipStream_t st);
 
+// One or two corrupt shards found from parity alone (cec_locate_multi_ptrs with max_bad = 2; the
+// rule is locate_multi_rule.h's). Rows and chunks as in LocatePlan; the planner tables hold all
+// four coefficient rows (loc2_put_set).
+struct PairPlan {
+  const uint64_t* rows;  // [nseg][rs], LocatePlan's
+  const uint8_t* sets;   // [set][set_bytes], loc2_put_set
+  uint64_t* witness;     // [nseg], preset to all ones: the lowest byte offset with some S_a != 0
+  uint64_t* witness2;    // [nseg], preset to all ones: the lowest byte offset with some T_a != 0
+                         // for a one-shard candidate (r = 4)
+  uint32_t* cand;        // [nseg]: the candidate word (loc2_pack1 / loc2_pack2) or 0xFFFFFFFF,
+                         // written for every segment by the first solve
+  uint8_t* dirty;        // [nseg], preset to 0: 1 where some syndrome byte is not zero
+  uint8_t* dirtyT;       // [nseg], preset to 0: 1 where some T byte is not zero
+  uint8_t* dirtyU;       // [nseg], preset to 0: 1 where some U byte is not zero
+  uint8_t* flags;        // [nseg][n], any alignment, written whole
+  uint8_t* status;       // [nseg]: kLoc* per segment
+  uint8_t* nbad;         // [nseg] or null: |J| of a FOUND segment, else 0
+  uint32_t rs, set_bytes;
+  uint32_t nseg;
+  int n, k, max_bad;
+};
+// The syndrome product k_pair_syn over all rows of bucket `nob`. mode 0: the locate pass (dirty,
+// witness: any syndrome). mode 1 (nob >= 2): the T confirm of the rows whose candidate is one
+// shard (dirtyT, and witness2 for nob = 4). mode 2 (nob = 4): the U confirm of the rows whose
+// candidate is a pair (dirtyU). Nothing else is stored.
+void launch_pair_syn(const PairPlan& p, int nob, int mode, uint64_t len, bool vec_ok,
+                     hipStream_t st);
+// One wave per segment. step 0: the candidate word from the shard bytes at the witness. step 1:
+// the second shard from the bytes at the second witness.
+void launch_pair_plan(const PairPlan& p, uint64_t len, int step, hipStream_t st);
+// One wave per segment: status, the n flag bytes and nbad.
+void launch_pair_finish(const PairPlan& p, hipStream_t st);
+// nbad[s] = 1 where status[s] is FOUND, else 0: the single rule's count.
+void launch_pair_nbad_single(const uint8_t* status, uint8_t* nbad, uint64_t nseg, hipStream_t st);
+
 // SHA-256 of `n` equal-length buffers, written as 64 lowercase hex characters each into
 // `hex_out` (device, n * 64 bytes). If `ptrs` is null, buffer i is shard (i % nshards) of
 // segment (i / nshards) in layout L.

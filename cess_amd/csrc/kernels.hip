@@ -24,6 +24,7 @@
 #include "dev_util.h"
 #include "flag_solve.h"
 #include "read_plan.h"
+#include "locate_multi_rule.h"
 #include "locate_rule.h"
 #include "gf256.h"
 #include "hashq_where.h"
@@ -2503,6 +2504,288 @@ void launch_locate_finish(const LocatePlan& p, hipStream_t st) {
   if (p.nseg == 0) return;
   hipLaunchKernelGGL(k_locate_finish, dim3((unsigned)(((uint64_t)p.nseg + 3) / 4)), dim3(256), 0,
                      st, p);
+}
+
+// ---------------------------------------------------------------------------------------------
+// One or two corrupt shards from parity alone (cec_locate_multi_ptrs with max_bad = 2;
+// locate_multi_rule.h states the rule, kernels.h PairPlan the tables). The product is
+// k_syn's, in pair_product, with three epilogues: the locate pass with the any-syndrome witness,
+// the T confirm for the rows whose candidate is one shard, which also lowers a second witness,
+// and the U confirm for the rows whose candidate is a pair. Locate pass, first solve, T confirm,
+// second solve, U confirm, finish, in that order on one stream. What lies between them is indexed
+// by segment and the same whatever order the waves ran in: a constant byte, a minimum, or a word
+// one wave writes.
+// ---------------------------------------------------------------------------------------------
+// One workgroup of the syndrome product over the table row `a`: syn_body's fold and Horner (the
+// byte tail goes to the last block, a call that is not vec_ok runs wholly byte-wise) with the
+// epilogue as a parameter. `judge(S, off)` gets the NOB syndromes of a lane's column, which starts
+// at byte offset `off`, and stores what they say; nothing else is written. (k_syn keeps its own
+// copy: built over this one, its four locate forms came out with four instructions of the byte
+// path in another order.)
+template <int NOB, class TV, int PF, class Judge>
+__device__ __forceinline__ void pair_product(const TableAddr& a, int vec_ok, Judge judge) {
+  const cu32* __restrict__ P = a.P;
+  const uint32_t nin = P[0];
+  const uint64_t len = a.len();
+  const cu32* __restrict__ masks = P + kRtHeaderWords;
+  auto fold = [&]<class T>(T (&t)[NOB][8], auto ld) CEC_AI {
+    T ring[PF];
+#pragma unroll
+    for (int q = 0; q < PF; ++q)
+      if (q < (int)nin) ring[q] = ld(a.key((uint64_t)q));
+    for (uint32_t j0 = 0; j0 < nin; j0 += PF) {
+#pragma unroll
+      for (int q = 0; q < PF; ++q) {
+        const uint32_t i = j0 + q;
+        if (i >= nin) break;  // wave-uniform
+        const T cur = ring[q];
+        if (i + PF < nin) ring[q] = ld(a.key((uint64_t)(i + PF)));
+        const cu32* __restrict__ mk = masks + i * 8 * NOB;
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+#pragma unroll
+          for (int o = 0; o < NOB; ++o) t[o][b] = bitop3_xand(t[o][b], cur, mk[b * NOB + o]);
+      }
+    }
+  };
+  auto horner = [&]<class T>(const T (&t)[NOB][8], uint64_t off) CEC_AI {
+    T S[NOB];
+#pragma unroll
+    for (int o = 0; o < NOB; ++o) {
+      T r = t[o][7];
+#pragma unroll
+      for (int b = 6; b >= 0; --b) r = xt(r) ^ t[o][b];
+      S[o] = r;
+    }
+    judge(S, off);
+  };
+  constexpr int VB = sizeof(TV);
+  if (vec_ok) {
+    const uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v < len / VB) {
+      TV t[NOB][8];
+#pragma unroll
+      for (int o = 0; o < NOB; ++o)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) t[o][b] = TV(0);
+      fold(t, [&](uint32_t key) CEC_AI { return ldv<true, TV>(a.in(key) + v * VB); });
+      horner(t, v * VB);
+    }
+    if (!(len % VB) || blockIdx.x != gridDim.x - 1) return;
+  }
+  // byte path: whole shard (vec_ok == 0, grid covers len) or the tail (last block)
+  const uint64_t i = vec_ok ? (len - len % VB) + threadIdx.x
+                            : (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= len) return;
+  uint32_t t[NOB][8];
+#pragma unroll
+  for (int o = 0; o < NOB; ++o)
+#pragma unroll
+    for (int b = 0; b < 8; ++b) t[o][b] = 0;
+  fold(t, [&](uint32_t key) CEC_AI -> uint32_t { return a.in(key)[i]; });
+  horner(t, i);
+}
+
+enum : int { kPairLocate = 0, kPairT = 1, kPairU = 2 };
+
+template <class T, int N>
+__device__ __forceinline__ T or_all(const T (&v)[N]) {
+  T acc = v[0];
+#pragma unroll
+  for (int o = 1; o < N; ++o) acc = acc | v[o];
+  return acc;
+}
+
+// The first lane of the wave whose column is not zero lowers the segment's witness to the
+// column's lowest non-zero byte: lanes hold ascending offsets, so that is the wave's lowest, with
+// one 64-bit atomic min per wave and pass at the most.
+template <class T>
+__device__ __forceinline__ void lower_witness(unsigned long long* wit, T any, uint64_t off) {
+  const unsigned long long m = __ballot(any_bits(any) != 0);
+  if (m && (threadIdx.x & 63) == (uint32_t)__ffsll(m) - 1)
+    atomicMin(wit, (unsigned long long)(off + first_nz_byte(any)));
+}
+
+// Rows as in k_syn. A T or U pass first loads the segment's candidate word, one scalar load, and
+// a row of the other kind or without a candidate ends there; a row without a chunk, or whose
+// chunk is of another bucket, as in k_syn.
+template <int NOB, class TV, int PF, int MODE>
+__global__ __launch_bounds__(256) void k_pair_syn(const uint64_t* __restrict__ tab, uint32_t row0,
+                                                  uint32_t rs, uint64_t len, int vec_ok,
+                                                  uint8_t* __restrict__ flags,
+                                                  uint64_t* __restrict__ witness,
+                                                  const uint32_t* __restrict__ cand) {
+  static_assert(MODE == kPairLocate || (MODE == kPairT && NOB >= 2) || (MODE == kPairU && NOB == 4));
+  const uint64_t r = row0 + blockIdx.y;
+  uint32_t c = 0;
+  if constexpr (MODE != kPairLocate) {
+    c = as_const(cand)[r];
+    if (loc2_nbad(c) != (MODE == kPairT ? 1u : 2u)) return;
+  }
+  if (tab_row(tab, r, rs)[0] == 0) return;
+  const TableAddr a(tab, r, rs, len);
+  if (a.P[2] != (uint32_t)NOB) return;
+  gu8* const flag = gptr((uint64_t)(uintptr_t)flags) + r;
+  unsigned long long* const wit = (unsigned long long*)(witness + r);
+  pair_product<NOB, TV, PF>(a, vec_ok, [&]<class T>(const T (&S)[NOB], uint64_t off) CEC_AI {
+    if constexpr (MODE == kPairLocate) {
+      const T any = or_all(S);
+      if (any_bits(any)) *flag = 1;
+      lower_witness(wit, any, off);
+    } else if constexpr (MODE == kPairT) {
+      const uint32_t j = loc2_j0(c);
+      T t[NOB - 1];
+#pragma unroll
+      for (int o = 0; o + 1 < NOB; ++o) t[o] = S[o + 1] ^ mul_uniform(j, S[o]);
+      const T any = or_all(t);
+      if (any_bits(any)) *flag = 1;
+      if constexpr (NOB == 4) lower_witness(wit, any, off);  // the second solve needs r = 4
+    } else {
+      const uint32_t sg1 = loc2_sigma1(c), sg2 = loc2_sigma2(c);
+      T u[2];
+#pragma unroll
+      for (int o = 0; o < 2; ++o)
+        u[o] = S[o + 2] ^ mul_uniform(sg1, S[o + 1]) ^ mul_uniform(sg2, S[o]);
+      if (any_bits(or_all(u))) *flag = 1;
+    }
+  });
+}
+
+// The two solves: one wave per segment, four per workgroup. The lanes stride over the held shards
+// (n may exceed 64), load one byte each at the witness offset and multiply it by the set's four
+// coefficient rows; an XOR reduction across the wave gives the packed S_0..S_3, then every held
+// lane tests its index and the ballots over all strides are counted. step 0: the column solve at
+// x1 for every dirty row with two or more checks. step 1: the second index at x2 from T, for the
+// rows whose single candidate left T dirty under the pair rule; every other row keeps its word.
+__global__ __launch_bounds__(256) void k_pair_plan(PairPlan p, uint64_t len, int step) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t s = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= p.nseg) return;  // the whole wave
+  const uint64_t* __restrict__ row = p.rows + s * p.rs;
+  const uint8_t* __restrict__ set = p.sets + row[p.rs - 1] * p.set_bytes;
+  const uint32_t h = loc_set_h(set), r = loc_set_r(set), n = (uint32_t)p.n;
+  uint32_t cand = step == 0 ? kLocNone : p.cand[s];
+  uint64_t x;
+  bool go = row[0] != 0 && p.dirty[s] != 0;  // wave-uniform, as everything below
+  if (step == 0) {
+    x = p.witness[s];
+    go = go && r >= 2;
+  } else {
+    x = p.witness2[s];
+    go = go && loc2_nbad(cand) == 1 && p.dirtyT[s] != 0 && loc2_pair_rule(r, (uint32_t)p.max_bad);
+  }
+  if (go && x < len) {  // no witness is all ones
+    const uint8_t* __restrict__ idx = loc2_set_idx(set);
+    uint32_t S = 0;
+    for (uint32_t t = lane; t < h; t += 64) S ^= loc2_term(set, n, t, gptr(row[1 + t])[x]);
+#pragma unroll
+    for (int d = 32; d; d >>= 1) S ^= (uint32_t)__shfl_xor((int)S, d);
+    if (step == 0) {
+      uint32_t ones = 0, j = 0, roots = 0, i01[2] = {0, 0};
+      if (loc2_s(S, 0))
+        for (uint32_t base = 0; base < h; base += 64) {
+          const uint32_t t = base + lane;
+          const unsigned long long m =
+              __ballot(t < h && loc2_one_matches(idx[t < h ? t : 0], S, r));
+          if (m && ones == 0) j = idx[base + (uint32_t)__ffsll(m) - 1];
+          ones += (uint32_t)__popcll(m);
+        }
+      if (ones != 1 && loc2_pair_rule(r, (uint32_t)p.max_bad)) {
+        const uint32_t locator = loc2_locator(S);
+        if (locator != kLocNone)
+          for (uint32_t base = 0; base < h; base += 64) {
+            const uint32_t t = base + lane;
+            unsigned long long m = __ballot(t < h && loc2_is_root(idx[t < h ? t : 0], locator));
+            for (; m; m &= m - 1, ++roots)
+              if (roots < 2) i01[roots] = idx[base + (uint32_t)__ffsll(m) - 1];
+          }
+      }
+      cand = loc2_solve1(ones, j, roots, i01[0], i01[1]);
+    } else {
+      const uint32_t j = loc2_j0(cand), T = loc2_t(j, S);
+      uint32_t hits = 0, i2 = 0;
+      if (loc2_s(T, 0))
+        for (uint32_t base = 0; base < h; base += 64) {
+          const uint32_t t = base + lane;
+          const unsigned long long m =
+              __ballot(t < h && loc2_second_matches(idx[t < h ? t : 0], j, T));
+          if (m && hits == 0) i2 = idx[base + (uint32_t)__ffsll(m) - 1];
+          hits += (uint32_t)__popcll(m);
+        }
+      cand = hits == 1 ? loc2_pack2(j, i2) : kLocNone;
+    }
+  } else if (step != 0) {
+    return;
+  }
+  if (lane == 0) p.cand[s] = cand;
+}
+
+// Status, flags and nbad of every segment by loc2_status and loc2_flag: one wave per segment, the
+// lanes stride over its n flag bytes.
+__global__ __launch_bounds__(256) void k_pair_finish(PairPlan p) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t s = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= p.nseg) return;  // the whole wave
+  const uint32_t n = (uint32_t)p.n;
+  const uint8_t* __restrict__ set = p.sets + p.rows[s * p.rs + p.rs - 1] * p.set_bytes;
+  const uint32_t cand = p.cand[s];
+  const uint32_t st = loc2_status(loc_set_h(set), (uint32_t)p.k, p.dirty[s] != 0, cand,
+                                  p.dirtyT[s] != 0, p.dirtyU[s] != 0);
+  if (lane == 0) {
+    p.status[s] = (uint8_t)st;
+    if (p.nbad) p.nbad[s] = (uint8_t)(st == kLocFound ? loc2_nbad(cand) : 0u);
+  }
+  const uint8_t* __restrict__ pos = loc2_set_pos(set, n);
+  uint8_t* __restrict__ fl = p.flags + s * n;
+  for (uint32_t i = lane; i < n; i += 64) fl[i] = (uint8_t)loc2_flag(st, pos[i] != 0, i, cand);
+}
+
+// nbad of the single rule (max_bad = 1 runs cec_locate_ptrs' kernels): 1 where FOUND
+__global__ __launch_bounds__(256) void k_pair_nbad_single(const uint8_t* __restrict__ status,
+                                                          uint8_t* __restrict__ nbad,
+                                                          uint64_t nseg) {
+  const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s < nseg) nbad[s] = status[s] == kLocFound ? 1 : 0;
+}
+
+void launch_pair_syn(const PairPlan& p, int nob, int mode, uint64_t len, bool vec_ok,
+                     hipStream_t st) {
+  if (p.nseg == 0 || (mode == kPairT && nob < 2) || (mode == kPairU && nob != 4)) return;
+  const int v = vec_ok ? 1 : 0;
+  rtb_dispatch(nob, [&]<int NOB, class TV, int PF>(RtbShape<NOB, TV, PF>) {
+    const unsigned gx = rt_grid_x(len, sizeof(TV), 1, vec_ok);
+    const uint32_t* const cand = p.cand;
+    if (mode == kPairLocate) {
+      launch_rows(k_pair_syn<NOB, TV, PF, kPairLocate>, gx, p.rows, p.nseg, st, p.rs, len, v,
+                  p.dirty, p.witness, cand);
+    } else if (mode == kPairT) {
+      if constexpr (NOB >= 2)
+        launch_rows(k_pair_syn<NOB, TV, PF, kPairT>, gx, p.rows, p.nseg, st, p.rs, len, v,
+                    p.dirtyT, p.witness2, cand);
+    } else {
+      if constexpr (NOB == 4)
+        launch_rows(k_pair_syn<NOB, TV, PF, kPairU>, gx, p.rows, p.nseg, st, p.rs, len, v,
+                    p.dirtyU, p.witness2, cand);
+    }
+  });
+}
+
+void launch_pair_plan(const PairPlan& p, uint64_t len, int step, hipStream_t st) {
+  if (p.nseg == 0) return;
+  hipLaunchKernelGGL(k_pair_plan, dim3((unsigned)(((uint64_t)p.nseg + 3) / 4)), dim3(256), 0, st,
+                     p, len, step);
+}
+
+void launch_pair_finish(const PairPlan& p, hipStream_t st) {
+  if (p.nseg == 0) return;
+  hipLaunchKernelGGL(k_pair_finish, dim3((unsigned)(((uint64_t)p.nseg + 3) / 4)), dim3(256), 0,
+                     st, p);
+}
+
+void launch_pair_nbad_single(const uint8_t* status, uint8_t* nbad, uint64_t nseg, hipStream_t st) {
+  if (nseg == 0) return;
+  hipLaunchKernelGGL(k_pair_nbad_single, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, st,
+                     status, nbad, nseg);
 }
 
 }  // namespace cec

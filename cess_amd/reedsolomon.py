@@ -673,6 +673,63 @@ class Encoder:
               "LocateDevice")
         return d_flags, d_status
 
+    def LocateMultiDevice(self, segments: Sequence, nsyn: int = _lib.CEC_LOCATE_SYN_MAX,
+                          max_bad: int = _lib.CEC_LOCATE_BAD_MAX, d_flags=None, d_status=None,
+                          d_nbad=None, stream=None):
+        """Find up to `max_bad` corrupt fragments of every segment from parity alone
+        (cec_locate_multi_ptrs): arguments and flags as in LocateDevice. With max_bad = 2 a
+        segment with r = min(nsyn, h - k) = 4 checks is FOUND with one or two shards (their flags
+        0, the other held flags 1) whenever at most two held shards disagree with the codeword of
+        the others; a segment with fewer checks gets the single rule. max_bad = 1 is LocateDevice.
+        locate_multi_host states the rule. Returns (d_flags uint8 [nseg, k + m], d_status uint8
+        [nseg], d_nbad uint8 [nseg]: the number of shards a FOUND segment names, else 0), the
+        given tensors or new ones; d_flags is what RepairFlaggedMultiDevice, ReadFlaggedDevice
+        and HashQueue.add_check_where_ptrs consume. ErrInvalidInput for a bad output tensor, for
+        `nsyn` outside 1..CEC_LOCATE_SYN_MAX and `max_bad` outside 1..CEC_LOCATE_BAD_MAX.
+        Enqueued on `stream` (default: torch's current stream) and not waited for; nothing is
+        copied to the host."""
+        import torch
+        if not 1 <= int(nsyn) <= _lib.CEC_LOCATE_SYN_MAX:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        if not 1 <= int(max_bad) <= _lib.CEC_LOCATE_BAD_MAX:
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        nseg, n = len(segments), self.Shards
+        dev = torch.device("cuda", self.device)
+        if d_flags is None:
+            d_flags = torch.empty((nseg, n), dtype=torch.uint8, device=dev)
+        elif (d_flags.dtype != torch.uint8 or d_flags.numel() != nseg * n or d_flags.device != dev
+              or not d_flags.is_contiguous()):
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        per_seg = []
+        for t in (d_status, d_nbad):
+            if t is None:
+                t = torch.empty(nseg, dtype=torch.uint8, device=dev)
+            elif (t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != nseg or t.device != dev
+                  or not t.is_contiguous()):
+                raise ErrInvalidInput(ErrInvalidInput.__doc__)
+            per_seg.append(t)
+        d_status, d_nbad = per_seg
+        if nseg == 0:
+            return d_flags, d_status, d_nbad
+        if self.ParityShards == 0:  # no parity, no check
+            raise ErrInvalidInput(ErrInvalidInput.__doc__)
+        ptrs = (c_void_p * (nseg * n))()
+        held = []
+        for s, shards in enumerate(segments):
+            if len(shards) != n:
+                raise ErrTooFewShards(ErrTooFewShards.__doc__)
+            for i, t in enumerate(shards):
+                if t is None:
+                    continue
+                held.append(_on_gpu(t, dev))
+                ptrs[s * n + i] = _dev_ptr(t)
+        size = self._check_device_shards(held) if held else 1
+        check(self._lib.cec_locate_multi_ptrs(self._h, ptrs, nseg, size, int(nsyn), int(max_bad),
+                                              _dev_ptr(d_flags), _dev_ptr(d_status),
+                                              _dev_ptr(d_nbad), self._device_stream(stream)),
+              "LocateMultiDevice")
+        return d_flags, d_status, d_nbad
+
     def ReconstructPartialDevice(self, shards: Sequence, present, out=None,
                                  accumulate: bool = False, stream=None) -> dict:
         """Partial rebuild of one segment in place (cec_reconstruct_partial_ptrs). `shards` is a
@@ -1150,6 +1207,27 @@ def locate_host(data_shards: int, parity_shards: int, shards, nsyn: int):
                                       sizes.pop() if sizes else 0, nsyn, byref(status),
                                       byref(found)), "locate_host")
     return status.value, found.value
+
+
+def locate_multi_host(data_shards: int, parity_shards: int, shards, nsyn: int, max_bad: int):
+    """Host only (cec_locate_multi_host): the rule Encoder.LocateMultiDevice applies to one
+    segment on the GPU, on host memory. `shards` as in locate_host. Returns (CEC_LOCATE_* status,
+    the shards of a FOUND segment ascending: a list of one or two, else empty)."""
+    n = data_shards + parity_shards
+    if len(shards) != n:
+        raise ValueError("shards must have k+m entries")
+    arrs = [None if s is None else np.frombuffer(s, np.uint8) if isinstance(s, bytes)
+            else _as_u8(s) for s in shards]
+    sizes = {a.size for a in arrs if a is not None}
+    if len(sizes) > 1:
+        raise ErrShardSize(ErrShardSize.__doc__)
+    ptrs = (c_void_p * n)(*[None if a is None else a.ctypes.data for a in arrs])
+    status, nfound, found = c_int(-1), c_int(0), (c_int * 2)(-1, -1)
+    check(_lib.load().cec_locate_multi_host(data_shards, parity_shards, ptrs,
+                                            sizes.pop() if sizes else 0, nsyn, max_bad,
+                                            byref(status), byref(nfound), found),
+          "locate_multi_host")
+    return status.value, [int(x) for x in found[:nfound.value]]
 
 
 def confirm_rule(status: int, ok) -> int:

@@ -540,9 +540,75 @@ int cec_locate_host(int k, int m, const uint8_t* const* shards, size_t shard_len
  * one byte of each held shard at the witness offset, the lowest offset with S_0 != 0 (a minimum,
  * so the result does not depend on the order in which waves ran); the confirm grids run where
  * there is a candidate; a last kernel writes status and flags. Not covered: two or more bad
- * shards per segment (they are AMBIGUOUS for up to r - 1 of them), shards in the batch layout. */
+ * shards per segment (they are AMBIGUOUS for up to r - 1 of them; cec_locate_multi_ptrs below
+ * names two with four checks), shards in the batch layout. */
 int cec_locate_ptrs(cec_codec* codec, const uint8_t* const* shards, size_t nseg, size_t shard_len,
                     int nsyn, uint8_t* d_flags, uint8_t* d_status, void* hip_stream);
+/* ---- two corrupt fragments found from parity alone ----------------------------------------------
+ * Bad shards B with errors e_i give S_a = XOR_{i in B} u_i i^a e_i: power sums with the shard
+ * indices as locators, so 2t syndromes locate t shards. The widest syndrome product computes four,
+ * which names two. The pair rule applies to a segment when max_bad >= 2 and r = min(nsyn, h - k) =
+ * 4; every other segment gets steps 1-3 with its r and is AMBIGUOUS past them.
+ *  1. Locate pass. dirty = some S_a != 0 somewhere; the witness x1 is the lowest byte offset at
+ *     which ANY of S_0..S_{r-1} is non-zero (two bad shards can cancel S_0 at every offset).
+ *  2. Column solve at x1. One index: S_0 != 0 and exactly one held j has S_{a+1} = j S_a for
+ *     every a < r - 1; J = {j}. Two indices (r = 4, one index failed): det = S_1^2 ^ S_0 S_2 != 0,
+ *     sigma1 = (S_1 S_2 ^ S_0 S_3) / det, sigma2 = (S_1 S_3 ^ S_2^2) / det, and exactly two held i
+ *     satisfy i^2 ^ sigma1 i ^ sigma2 = 0; J = those two. Neither: AMBIGUOUS.
+ *  3. Confirm with |J| = 1. T_a = S_{a+1} ^ j S_a (a < r - 1) zero everywhere: FOUND {j}.
+ *     Otherwise, with the pair rule, x2 is the lowest offset at which any T_a is non-zero; there
+ *     T_0 != 0 and exactly one held i != j must satisfy T_1 = i T_0 and T_2 = i T_1; J = {j, i},
+ *     sigma1 = j ^ i, sigma2 = j i. Any other outcome: AMBIGUOUS.
+ *  4. Confirm with |J| = 2. U_a = S_{a+2} ^ sigma1 S_{a+1} ^ sigma2 S_a (a = 0, 1) zero
+ *     everywhere: FOUND J. Otherwise AMBIGUOUS.
+ * Statuses are the four CEC_LOCATE_* codes; FOUND covers one or two shards. FOUND: the shards of J
+ * have flag 0, the other held shards 1. AMBIGUOUS: every held flag 0. Not held: 0. nbad = |J| for
+ * FOUND, else 0.
+ * The guarantee and its limit: with r = 4 the four checks define a code of distance 5 on H. If the
+ * held shards that differ from the codeword of the others are a set B with |B| <= 2, the result is
+ * FOUND with exactly B: the column at x1 has error weight 1 or 2 inside B and decoding is unique
+ * within radius 2; the held set without j has three checks and distance 4, which names the other
+ * shard at x2; the pair confirm has two checks. A wrong FOUND needs an error of weight >= 3 outside
+ * J at every offset where one exists, so it needs |B| >= 3: cec_confirm_flagged covers that case,
+ * as it does for the single rule at |B| >= r. */
+#define CEC_LOCATE_BAD_MAX (2)
+/* Host only: the rule on host memory, by the device code's own functions
+ * (csrc/locate_multi_rule.h) with loops in place of lanes. shards as in cec_locate_host. *status
+ * receives the CEC_LOCATE_* code, *nfound |J| of a FOUND segment (else 0), found[0..2) its shards
+ * ascending, unused entries -1. max_bad == 1 is cec_locate_host's rule, by its code. CEC_EINVAL: a
+ * NULL pointer, nsyn or max_bad out of range, k, m out of the codec's range; nothing is written. */
+int cec_locate_multi_host(int k, int m, const uint8_t* const* shards, size_t shard_len, int nsyn,
+                          int max_bad, int* status, int* nfound, int found[2]);
+/* The call. shards, d_flags and d_status as in cec_locate_ptrs. d_nbad: nseg DEVICE bytes, or NULL.
+ * max_bad == 1 runs cec_locate_ptrs' own launches: d_flags and d_status are byte-equal to that
+ * call's on every input.
+ *  - Reads: the held shards of segments with h > k, once; those of a dirty segment with a
+ *    candidate once more; those of a segment whose two bad shards do not meet at the first dirty
+ *    offset a third time. Nothing of an UNCHECKED segment is read.
+ *  - Writes: d_flags, d_status and, where given, d_nbad, and nothing else. No shard is written.
+ *  - Not waited for: everything is enqueued on hip_stream, nothing is copied to the host. (It
+ *    waits for the codec's own upload stream, for its table, as the other _ptrs calls do.)
+ *  - Validation: before anything is enqueued; an error writes no byte. CEC_EINVAL: a NULL codec;
+ *    with nseg > 0 a NULL shards, d_flags or d_status; nsyn outside [1, CEC_LOCATE_SYN_MAX];
+ *    max_bad outside [1, CEC_LOCATE_BAD_MAX]. CEC_ESHARDLEN: shard_len == 0. nseg == 0: CEC_OK.
+ *    Shard addresses may alias: they are only read.
+ *  - Alignment: any; 16-byte-aligned held addresses give vector columns with a byte tail,
+ *    otherwise the whole call runs byte-wise.
+ *  - Memory: one block from the codec's pool, retired behind the launches (CEC_STAT_POOL_BYTES
+ *    does not grow across repeated calls): per segment a row of 8(most + 2) bytes and 23 bytes of
+ *    state (14 with max_bad == 1); per distinct held set a planner table of 6n + 8 bytes (4n + 8)
+ *    and one program chunk of 4(772 + 8hr) bytes. The decode cache is neither read nor filled
+ *    (CEC_STAT_DECODE_CACHED does not change).
+ *  - HIP graph capture: not capturable, for the reasons given at cec_reconstruct_ptrs.
+ * With max_bad == 2: one locate grid per value of r in the call; a planner wave per segment for
+ * the column solve at x1; one T-confirm grid per r >= 2 for the rows with one candidate; with
+ * r = 4 in the call a second planner launch (the second index at x2) and one U-confirm grid for
+ * the rows with a pair; a last kernel writes status, flags and nbad. Every value between the
+ * launches is a constant byte, a minimum or a word one wave writes. Not covered: more than two bad
+ * shards or more than four syndromes, the pair rule for r < 4, shards in the batch layout. */
+int cec_locate_multi_ptrs(cec_codec* codec, const uint8_t* const* shards, size_t nseg,
+                          size_t shard_len, int nsyn, int max_bad, uint8_t* d_flags,
+                          uint8_t* d_status, uint8_t* d_nbad, void* hip_stream);
 /* ---- parity accumulated shard by shard (klauspost EncodeIdx and Update) -----------------------
  * Both are one primitive on the codec's encode matrix E (cec_matrix; row k+o is parity shard o):
  *   parity[o] ^= E[k+o][j] * x_j   for every o < m,

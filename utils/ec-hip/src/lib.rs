@@ -218,6 +218,14 @@ pub mod sys {
         pub fn cec_locate_ptrs(c: *mut cec_codec, shards: *const *const u8, nseg: usize,
                                shard_len: usize, nsyn: c_int, d_flags: *mut u8,
                                d_status: *mut u8, stream: *mut c_void) -> c_int;
+        pub fn cec_locate_multi_host(k: c_int, m: c_int, shards: *const *const u8,
+                                     shard_len: usize, nsyn: c_int, max_bad: c_int,
+                                     status: *mut c_int, nfound: *mut c_int,
+                                     found: *mut c_int) -> c_int;
+        pub fn cec_locate_multi_ptrs(c: *mut cec_codec, shards: *const *const u8, nseg: usize,
+                                     shard_len: usize, nsyn: c_int, max_bad: c_int,
+                                     d_flags: *mut u8, d_status: *mut u8, d_nbad: *mut u8,
+                                     stream: *mut c_void) -> c_int;
         pub fn cec_encode_idx_batch(c: *mut cec_codec, d_shard: *const u8,
                                     shard_seg_stride: usize, idx: c_int, d_parity: *mut u8,
                                     nseg: usize, shard_len: usize, accumulate: c_int,
@@ -450,6 +458,7 @@ pub const CEC_LOCATE_CLEAN: c_int = 0;
 pub const CEC_LOCATE_FOUND: c_int = 1;
 pub const CEC_LOCATE_AMBIGUOUS: c_int = 2;
 pub const CEC_LOCATE_UNCHECKED: c_int = 3;
+pub const CEC_LOCATE_BAD_MAX: c_int = 2;
 pub const CEC_CONFIRM_NONE: c_int = 0;
 pub const CEC_CONFIRM_PROVEN: c_int = 1;
 pub const CEC_CONFIRM_REFUTED: c_int = 2;
@@ -883,6 +892,49 @@ impl ReedSolomon {
                             &mut status, &mut found)
         })?;
         Ok((status, if found >= 0 { Some(found as usize) } else { None }))
+    }
+
+    /// Find up to `max_bad` corrupt shards of every segment from parity alone
+    /// (`cec_locate_multi_ptrs`): arguments as in `locate_ptrs`, plus `max_bad` in
+    /// `1..=CEC_LOCATE_BAD_MAX` and `d_nbad`, one byte per segment or null, which receives the
+    /// number of shards a `CEC_LOCATE_FOUND` segment names (0 for every other status). Two shards
+    /// are named only where four checks are computed (`nsyn` = 4 and k + 4 or more shards held);
+    /// `max_bad` = 1 is `locate_ptrs`. Enqueued on `stream` and not waited for.
+    ///
+    /// # Safety
+    /// As for `locate_ptrs`; a non-null `d_nbad` must be device memory of one byte per segment.
+    pub unsafe fn locate_multi_ptrs(&self, shards: &[*const u8], shard_len: usize, nsyn: i32,
+                                    max_bad: i32, d_flags: *mut u8, d_status: *mut u8,
+                                    d_nbad: *mut u8, stream: *mut c_void) -> Result<(), Error> {
+        let n = self.k + self.m;
+        if shards.len() % n != 0 {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        check(cec_locate_multi_ptrs(self.c, shards.as_ptr(), shards.len() / n, shard_len,
+                                    nsyn as c_int, max_bad as c_int, d_flags, d_status, d_nbad,
+                                    stream))
+    }
+
+    /// The rule `locate_multi_ptrs` applies to one segment, on host memory
+    /// (`cec_locate_multi_host`): returns the `CEC_LOCATE_*` status and the shards of a
+    /// `CEC_LOCATE_FOUND` segment, ascending (one or two).
+    pub fn locate_multi_host(&self, shards: &[Option<&[u8]>], nsyn: i32,
+                             max_bad: i32) -> Result<(i32, Vec<usize>), Error> {
+        let n = self.k + self.m;
+        let len = shards.iter().flatten().map(|s| s.len()).next().unwrap_or(0);
+        if shards.len() != n || shards.iter().flatten().any(|s| s.len() != len) {
+            return Err(Error::from_code(CEC_EINVAL));
+        }
+        let ptrs: Vec<*const u8> =
+            shards.iter().map(|s| s.map_or(std::ptr::null(), |b| b.as_ptr())).collect();
+        let (mut status, mut nfound): (c_int, c_int) = (0, 0);
+        let mut found: [c_int; 2] = [-1, -1];
+        check(unsafe {
+            cec_locate_multi_host(self.k as c_int, self.m as c_int, ptrs.as_ptr(), len,
+                                  nsyn as c_int, max_bad as c_int, &mut status, &mut nfound,
+                                  found.as_mut_ptr())
+        })?;
+        Ok((status, found[..nfound as usize].iter().map(|&i| i as usize).collect()))
     }
 
     /// EncodeIdx on scattered device shards in place (`cec_encode_idx_ptrs`): `data` holds
